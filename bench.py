@@ -21,11 +21,20 @@ non-zero when fewer than N GPUs are visible.
 Prints ONE JSON line on rank 0.  `value` = filter-steps/s over all GPUs (the slowest rank's wall
 clock, the final gather included).  `roofline` is the fused kernel's achieved algorithmic HBM read rate per
 GPU (40 B x filters x records / kernel time, HIP events on the launch stream) against the 8 TB/s
-peak; `valu_roofline` is the resource that binds it, FP64 VALU issue; `cpu_baseline` times the
-NumPy restatement of the reference loop on the job's host cores (rank 0, at every N, a bounded
-sample, before any GPU work; the core count comes from the cgroup's CPU quota / cpuset);
-`kernel_ms_per_gpu` / `gather_ms_per_gpu` attribute each GPU's time to its launches and the gather.
+peak; `valu_roofline` is the resource that binds it, FP64 VALU issue (both are arithmetic on the
+timed steps' own HIP events); `kernel_ms_per_gpu` / `gather_ms_per_gpu` attribute each GPU's time
+to its launches and the gather.
 A rank that never joins or dies mid-run fails the job within PEKF_COMM_TIMEOUT_S (status 2).
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what takes work
+of its own: `cpu_baseline` times the NumPy restatement of the reference loop on the job's host
+cores (rank 0, at every N, a bounded sample, before any GPU work; the core count comes from the
+cgroup's CPU quota / cpuset), and `parity` re-runs sampled filters with the C oracle; without
+`--full` both are null.  `--dump-outputs DIR` writes, after the timed steps, what the last step
+left for its caller as DIR/<name>.npy (float64): `quaternions` (every filter's final X on rank 0,
+the gathered rows when a gather ran) and `covariance` (the final P of rank 0's shard); an array
+beyond its share of 64 MB is cut to a fixed, seeded sample of its rows.  The inputs depend only
+on the arguments, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -385,6 +394,10 @@ class RankRun:
         X, _ = self.filt.get_state()
         return self.first, X
 
+    def final_covariance(self):
+        """P (B, 4, 4) of this rank's shard after the last step."""
+        return self.filt.get_state()[1]
+
     def close(self):
         if self.comm is not None:
             self.comm.close()
@@ -474,6 +487,11 @@ class MultiRun:
     def final_rows(self):
         return 0, self.m.gathered()
 
+    def final_covariance(self):
+        """P (B, 4, 4) of the first device's shard after the last step."""
+        self.engine.set_device(self.devices[0])
+        return self.m.filts[0].get_state()[1]
+
     def close(self):
         self.m.close()
 
@@ -498,6 +516,27 @@ def parity_check(first, rows, n_samples, n_records, args):
                                                                           atol=1e-12))}
 
 
+DUMP_BYTES = {"quaternions": 32 << 20, "covariance": 16 << 20}   # 48 MB of the 64 MB a dump may take
+DUMP_SAMPLE_SEED = 20261019
+
+
+def dump_outputs(directory, arrays):
+    """Writes arrays[name] as directory/<name>.npy (float64).  An array larger than DUMP_BYTES[name] is
+    cut to a sample of its rows: sorted row indices drawn without replacement by a generator seeded
+    with DUMP_SAMPLE_SEED, so the same shape always gives the same rows."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        keep = DUMP_BYTES[name] // (a.nbytes // a.shape[0])
+        if a.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], keep, replace=False))
+            log("dump: %s cut to a seeded sample of %d of its %d rows" % (name, keep, a.shape[0]))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        log("dump: %s %s -> %s" % (name, a.shape, os.path.join(directory, name + ".npy")))
+
+
 # ----------------------------------------------------------------------------------- main
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -509,12 +548,18 @@ def parse_args(argv=None):
     ap.add_argument("--window", type=int, default=1024, help="resident records per filter")
     ap.add_argument("--missing", action="store_true", help="config 5: 30%% magnetometer-missing records")
     ap.add_argument("--seed", type=int, default=20261015)
-    ap.add_argument("--cpu-baseline", choices=["port", "none"], default="port")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline and check sampled filters against the C oracle "
+                         "(off by default: a plain run does only what its headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--cpu-baseline", choices=["port", "none"], default="port",
+                    help="with --full: the CPU baseline to time")
     ap.add_argument("--cpu-filters-per-core", type=int, default=160,
                     help="CPU baseline sample: filters per host process")
     ap.add_argument("--cpu-records", type=int, default=1500, help="CPU baseline sample: records per filter")
     ap.add_argument("--parity-samples", type=int, default=16,
-                    help="filters re-run by the C oracle (at least 4 per GPU when N > 1)")
+                    help="with --full: filters re-run by the C oracle (at least 4 per GPU when N > 1)")
     ap.add_argument("--precision", choices=["f64", "mixed"], default="f64",
                     help="f64 (default, as the reference) or mixed (covariance recursion in f32)")
     ap.add_argument("--dist", action="store_true",
@@ -560,10 +605,10 @@ def _main(argv=None):
         rdzv = shard.FileRendezvous(rank, world)
 
     try:
-        # CPU baseline first (rank 0, every N), in forked workers, before anything touches the GPU;
-        # the other ranks wait for rank 0's RCCL id meanwhile.
+        # --full: CPU baseline first (rank 0, every N), in forked workers, before anything touches the
+        # GPU; the other ranks wait for rank 0's RCCL id meanwhile.
         cpu = None
-        if args.cpu_baseline == "port" and rank == 0:
+        if args.full and args.cpu_baseline == "port" and rank == 0:
             log("cpu baseline (NumPy restatement) ...")
             cpu = cpu_baseline(args.seed, args.missing, args.cpu_filters_per_core, args.cpu_records)
             try:
@@ -615,10 +660,13 @@ def _main(argv=None):
          ", ".join("%.3f" % v for v in per_gpu[1])))
 
     # final quaternions of every GPU's filters on rank 0 (the gathered rows), then all ranks part
-    rows = run.final_rows() if rank == 0 and args.parity_samples > 0 else None
+    want_parity = args.full and args.parity_samples > 0
+    rows = run.final_rows() if rank == 0 and (want_parity or args.dump_outputs) else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"quaternions": rows[1], "covariance": run.final_covariance()})
     run.barrier()
     parity = None
-    if rows is not None:
+    if rows is not None and want_parity:
         samples = max(args.parity_samples, 4 * world)
         parity = parity_check(rows[0], rows[1], samples, total * N, args)
         log("parity: max |dq| = %.3e over %d sampled filters of shards %s" %

@@ -7,7 +7,7 @@ set -u
 out=$1
 mkdir -p "$out"
 for r in 0 1 2 3 4 5 6 7; do
-  timeout -k 10 200 python3 bench.py --shard-of $r/8 --cpu-baseline none --steps 3 --warmup 1 \
+  timeout -k 10 200 python3 bench.py --full --shard-of $r/8 --cpu-baseline none --steps 3 --warmup 1 \
       --parity-samples 32 > "$out/shard_$r.json" 2> "$out/shard_$r.log" || exit $?
   grep -h "timed:\|parity:" "$out/shard_$r.log"
 done

@@ -19,14 +19,14 @@ steps=(
  "timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o run --output-format csv -- $B --steps 1 --warmup 0"
  "timeout -s KILL 120 rocprofv3 --pmc $SQ -d $O/pmc_sq -o run --output-format csv -- $B --steps 1 --warmup 0"
  "python3 scripts/pmc_summary.py $O/pmc_fetch/run_counter_collection.csv $O/pmc_sq/run_counter_collection.csv 1048576 10000 $rdir/pmc_summary_c3.json && cp $rdir/pmc_summary_c3.json $O/ && cp $O/trace/run_kernel_stats.csv $rdir/kernel_stats_c3.csv && cp $O/trace/run_kernel_stats.csv $O/"
- "timeout -k 10 400 python bench.py > $O/bench_c3_f64.json"
+ "timeout -k 10 400 python bench.py --full > $O/bench_c3_f64.json"
 )
 if [ "$mode" = full ]; then
  steps+=(
- "timeout -k 10 300 python bench.py --batch 65536 --cpu-baseline none > $O/bench_c2_f64.json"
- "timeout -k 10 300 python bench.py --missing --cpu-baseline none > $O/bench_c5_f64.json"
- "timeout -k 10 300 python bench.py --precision mixed --cpu-baseline none > $O/bench_c3_mixed.json"
- "timeout -k 10 300 python bench.py --dist --cpu-baseline none --steps 2 > $O/bench_dist1.json"
+ "timeout -k 10 300 python bench.py --full --batch 65536 --cpu-baseline none > $O/bench_c2_f64.json"
+ "timeout -k 10 300 python bench.py --full --missing --cpu-baseline none > $O/bench_c5_f64.json"
+ "timeout -k 10 300 python bench.py --full --precision mixed --cpu-baseline none > $O/bench_c3_mixed.json"
+ "timeout -k 10 300 python bench.py --full --dist --cpu-baseline none --steps 2 > $O/bench_dist1.json"
  "timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/auxtrace -o aux --output-format csv -- python3 scripts/bench_aux.py > $O/aux_bench.json"
  )
 fi

@@ -25,7 +25,7 @@ import pytest
 
 from .conftest import ROOT
 
-SMALL = ["--batch", "256", "--records", "16", "--window", "8", "--steps", "2", "--warmup", "1",
+SMALL = ["--batch", "256", "--records", "16", "--window", "8", "--steps", "2", "--warmup", "1", "--full",
          "--cpu-filters-per-core", "2", "--cpu-records", "10", "--parity-samples", "16"]
 
 
@@ -81,6 +81,56 @@ def test_one_process_eight_devices(monkeypatch, capfd):
     assert fake.calls.count("pekf_gather_multi_dev") == 2          # after the warmup + ONE after the timed steps
     assert sorted({r[0] for r in fake.runs}) == list(range(8))     # every device ran its shard
     assert all(r[1:] == (256, 16, (k // 8) * 16 % 8) for k, r in enumerate(fake.runs))
+
+
+PLAIN = ["--batch", "256", "--records", "16", "--window", "8", "--steps", "3", "--warmup", "1"]
+
+
+def test_plain_run_times_the_steps_and_nothing_else(monkeypatch, capfd, tmp_path):
+    """Without --full: no CPU baseline, no oracle comparison, --steps launches timed; --dump-outputs
+    writes the last step's X and P, the same arrays from run to run, equal to the oracle's run."""
+    from . import fake_libpekf
+    from oracle import oracle_c
+    from poseestimationkf_amd import synth
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    fake = fake_libpekf.install(monkeypatch, n_devices=1)
+    bench = _bench()
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("CPU baseline in a plain run"))
+    monkeypatch.setattr(bench, "parity_check", lambda *a, **k: pytest.fail("parity check in a plain run"))
+    got = []
+    for d in ("a", "b"):
+        bench.main(["--gpus", "1", "--dump-outputs", str(tmp_path / d)] + PLAIN)
+        out, _ = capfd.readouterr()
+        line = _one_line(out)
+        assert line["cpu_baseline"] is None and line["parity"] is None
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f64"
+        assert line["value"] == pytest.approx(256 * 16 * 3 / (line["ms_per_step"] * 3 / 1e3))
+        assert sorted(os.listdir(tmp_path / d)) == ["covariance.npy", "quaternions.npy"]
+        got.append({n: np.load(tmp_path / d / (n + ".npy")) for n in ("quaternions", "covariance")})
+    assert fake.runs == [(0, 256, 16, k * 16 % 8) for k in range(4)] * 2     # 1 warmup + 3 timed, per run
+    for n, shape in (("quaternions", (256, 4)), ("covariance", (256, 4, 4))):
+        assert got[0][n].dtype == np.float64 and got[0][n].shape == shape
+        assert np.array_equal(got[0][n], got[1][n])
+    rec = synth.generate(np.arange(256), 8, seed=bench.parse_args([]).seed)
+    Xo, Po, _ = oracle_c.run(rec, n_steps=4 * 16)
+    assert np.array_equal(got[0]["quaternions"], Xo) and np.array_equal(got[0]["covariance"], Po)
+
+
+def test_dump_outputs_samples_large_arrays_the_same_way_every_time(tmp_path, monkeypatch):
+    bench = _bench()
+    assert sum(bench.DUMP_BYTES.values()) <= 64 << 20
+    monkeypatch.setitem(bench.DUMP_BYTES, "covariance", 100 * 128)
+    P = np.arange(1000 * 16, dtype=np.float64).reshape(1000, 4, 4)
+    X = np.arange(1000 * 4, dtype=np.float32).reshape(1000, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"quaternions": X, "covariance": P})
+    a, b = np.load(tmp_path / "a" / "covariance.npy"), np.load(tmp_path / "b" / "covariance.npy")
+    assert a.shape == (100, 4, 4) and np.array_equal(a, b)
+    rows = (a[:, 0, 0] / 16).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, P[rows])           # whole rows, in order
+    q = np.load(tmp_path / "a" / "quaternions.npy")
+    assert q.dtype == np.float64 and np.array_equal(q, X)
 
 
 def _rank_main(rank, world, env, out_path, n_devices):
