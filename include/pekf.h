@@ -340,6 +340,34 @@ int pekf_frontend_init_ext_dev(int64_t batch, int64_t n_events, const void *ev_p
                                int n_avg, double *init, int64_t *t_init, double *stats, int32_t *ready,
                                uint32_t flags, void *stream);
 
+/* Phase 1 of the server's client session (KFS/Magnetometer_Calibration.cpp) on the device: per phone, the
+ * magnetometer's hard-iron bias and soft-iron matrix W from its phase-1 messages.  Events as for
+ * pekf_frontend_init_dev (ev_planes [n_events][batch]; times are not used).  Every message is a sample,
+ * whatever its type (KFS/Parser.cpp:30-34,144-147 ignores Type); time events and FP64 no-message events are
+ * not messages.  The first n_cal (the server: 100) samples are kept; message n_cal + 1 fires the fit
+ * (setValues, :13-43), so a phone with n_cal messages or fewer is not calibrated.  bias = their FP64 sum in
+ * arrival order / n_cal (:20-22,32-34; bit for bit the reference's).  With v = m - bias, {a,b,c,d,e,f} is the
+ * least-squares solution of [x^2, y^2, z^2, 2xy, 2zx, 2yz] . {a..f} = 1 over those samples (:65-80,159-164;
+ * normal equations summed in FP64 from zero, unpivoted Cholesky), R = [[a,d,e],[d,b,f],[e,f,c]] (:165-175) and
+ * W = V sqrt(D) V^T, R's principal square root (:178-200; cyclic Jacobi, fixed pair order and sweep count).
+ * status[b]: 0 calibrated; 1 n_cal or fewer messages; 2 a Cholesky pivot <= 0 or not finite (the samples do
+ * not determine a quadric, e.g. a phone that was never turned); 3 an eigenvalue of R <= 0 or not finite (not
+ * an ellipsoid).  For status != 0: bias 0, W = I, fit NaN.
+ * cal[batch*12] = {bias xyz, W row-major 3x3 (symmetric, mirrored entries bit-equal)};
+ * fit[batch*6] = {a,b,c,d,e,f} (may be NULL); status[batch]; flags: PEKF_EV_F64_EVENTS
+ * (PEKF_EV_TIME_EVENTS accepted and honoured always, as phase 2).  n_cal >= 6. */
+int pekf_magcal_dev(int64_t batch, int64_t n_events, const void *ev_planes, int n_cal,
+                    double *cal, double *fit, int32_t *status, uint32_t flags, void *stream);
+/* The correction (the commented body of CorrectValues, :46-55), in place on an event plane of phase 2 or 3:
+ * every magnetometer event (type 2) of a phone whose status is 0 becomes W (m - bias); every other event,
+ * time events and no-message events, and every column whose status != 0 are not written (bit for bit as they
+ * were).  f32 planes: computed in FP64, rounded to f32.  The server corrects the raw sample in phase 2
+ * (KFS/Parser.cpp:107) and the interpolated one in phase 3 (:239); the correction is affine, so correcting
+ * phase 3's raw samples here equals that in real arithmetic -- within rounding, not bit for bit.
+ * status may be NULL (every phone calibrated). */
+int pekf_magcal_apply_dev(int64_t batch, int64_t n_events, void *ev_planes, const double *cal,
+                          const int32_t *status, uint32_t flags, void *stream);
+
 /* The wire on the device: the clients' 100-byte frames (as MessageSender.java:217-233 sends and Server.cpp:35,84
  * receives them: "#<phase>,<type>:<x>,<y>,<z>,t:<ns>", spaces to 99 characters, '\n') -> FP64 event planes.
  * frames: [n_frames][batch][100] bytes (device; 4-byte aligned), phone b's frames in order along the first

@@ -3,9 +3,10 @@
 Layout
   csrc/        HIP kernels for gfx950 + the C ABI of include/pekf.h  -> libpekf.so
   _lib.py      ctypes binding (no PyTorch; raises if libpekf.so is missing)
-  engine.py    device buffers, resident IMU windows, BatchedEKF (fused kernel), batched per-call ops
+  engine.py    device buffers, resident IMU windows, BatchedEKF (fused kernel), batched per-call ops,
+               the server's session: calibrate_magnetometer (phase 1), run_session / run_wire_session
   dropin/      ExtendedKalmanFilter / Wahba / UtilityFunctions / ReadFile with the reference's API
-  synth.py     host mirror of the device Philox IMU generator (bit-identical)
+  synth.py     host mirror of the device Philox IMU generator (bit-identical); event and calibration streams
   logformat.py the live server's text log (emit / ingest)
   shard.py     filter-batch sharding over ranks + the final-quaternion gather
 

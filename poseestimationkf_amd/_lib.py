@@ -117,6 +117,8 @@ SIGNATURES = {
     "pekf_frontend_ext_dev": [_i64, _i64, _vp, _vp, _vp, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp],
     "pekf_frontend_init_dev": [_i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "pekf_frontend_init_ext_dev": [_i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _u32, _vp],
+    "pekf_magcal_dev": [_i64, _i64, _vp, _int, _vp, _vp, _vp, _u32, _vp],
+    "pekf_magcal_apply_dev": [_i64, _i64, _vp, _vp, _vp, _u32, _vp],
     "pekf_f32_wire_values": [_i64, _vp, _vp],
     "pekf_wire_parse": [ctypes.c_char_p, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64)],
     "pekf_wire_events_dev": [_i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

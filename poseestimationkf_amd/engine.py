@@ -469,6 +469,36 @@ def frontend_init(ev, n_avg=100, stats=True, events="f32"):
     return out
 
 
+def calibrate_magnetometer(ev, n_cal=100, events="f32"):
+    """Phase-1 events (synth.generate_calibration_events layout, or wire.events_from_wire(..., phase=1)) ->
+    each phone's magnetometer calibration by pekf_magcal_dev (KFS/Magnetometer_Calibration.cpp): dict(bias
+    (K, 3), W (K, 3, 3), fit (K, 6) the quadric {a, b, c, d, e, f}, status (K,) int32 (include/pekf.h: 0
+    calibrated, 1 n_cal or fewer messages, 2 the samples determine no quadric, 3 not an ellipsoid),
+    calibrated (K,) bool, cal / status_dev the device buffers run_session / run_wire_session take).  A phone
+    that is not calibrated has bias 0, W = I and fit NaN, and its samples are left as they are.
+    events: as run_frontend."""
+    K = np.asarray(ev["types"]).shape[1]
+    if "t_init" not in ev:
+        ev = dict(ev, t_init=np.zeros(K, np.int64))
+    evb, E, flags = _event_planes(ev, events)
+    cal, fit, st = DeviceBuffer(96 * K), DeviceBuffer(48 * K), DeviceBuffer(4 * K)
+    check(lib.pekf_magcal_dev(K, E, evb.ptr, int(n_cal), cal.ptr, fit.ptr, st.ptr, flags & EV_F64_EVENTS, None))
+    check(lib.pekf_device_sync())
+    c = cal.download((K, 12), np.float64)
+    status = st.download((K,), np.int32)
+    return dict(bias=c[:, :3].copy(), W=c[:, 3:].reshape(K, 3, 3).copy(), fit=fit.download((K, 6), np.float64),
+                status=status, calibrated=status == 0, cal=cal, status_dev=st)
+
+
+def _apply_calibration(calibration, batch, n_events, ev_ptr, flags, stream=None):
+    """pekf_magcal_apply_dev on device event planes (enqueued): the magnetometer events of the calibrated
+    phones become W (m - bias)."""
+    if len(calibration["status"]) != batch:
+        raise ValueError("the calibration is of %d phones, the session of %d" % (len(calibration["status"]), batch))
+    check(lib.pekf_magcal_apply_dev(batch, int(n_events), ev_ptr, calibration["cal"].ptr,
+                                    calibration["status_dev"].ptr, flags & EV_F64_EVENTS, stream))
+
+
 def _record_flags(records, events="f32"):
     """pekf_live_ext_dev's record precision: "f64" (the low-pass acc / mag as the server's filter gets them,
     KFS/KalmanFilter.cpp:279-303) or "f32" (the 40 B stream record, as the split pipeline's).  FP64 events
@@ -480,13 +510,16 @@ def _record_flags(records, events="f32"):
     return EV_F32_RECORDS if records == "f32" else 0
 
 
-def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", events="f32"):
+def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", events="f32", calibration=None):
     """A whole client session of the server on the device (KFS/Parser.cpp:28-72): phase-2 events ->
     initial means and start time (pekf_frontend_init_dev) -> phase-3 events -> records -> the filters'
     state (pekf_live_dev), the phase-2 results handed over in device memory.  phase3's times continue
     phase2's (its first gap is taken from phase2's last event, the time phase 3 starts from).
     filters: a BatchedEKF (FP64, AoS) whose state is advanced; records and events as
     BatchedEKF.run_events.
+    calibration: calibrate_magnetometer's dict (phase 1): the magnetometer samples of both phases are
+    corrected on the device first (pekf_magcal_apply_dev; the server's CorrectValues call sites,
+    KFS/Parser.cpp:107,239), and the returned dict has calibrated (K,) bool.  None: no correction, no launch.
     Returns dict(ready (K,) bool -- a filter
     that never finished phase 2 has NaN references, applies no record and keeps its state --, counts
     (K,) records applied, refs (K, 6))."""
@@ -498,13 +531,19 @@ def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", ev
     ev3, E3, flags3 = _event_planes(dict(phase3, t_init=t_last), events)
     tsb = DeviceBuffer(8 * K).upload(np.ascontiguousarray(phase2["t_init"], np.int64))
     ib, tib, rb = DeviceBuffer(48 * K), DeviceBuffer(8 * K), DeviceBuffer(4 * K)
+    if calibration is not None:
+        _apply_calibration(calibration, K, E2, ev2.ptr, flags2)
+        _apply_calibration(calibration, K, E3, ev3.ptr, flags3)
     check(lib.pekf_frontend_init_ext_dev(K, E2, ev2.ptr, tsb.ptr, int(n_avg), ib.ptr, tib.ptr, None, rb.ptr,
                                          flags2 & EV_F64_EVENTS, None))
     cnt, refs = DeviceBuffer(4 * K), DeviceBuffer(48 * K)
     filters.run_events_async(ev3, E3, ib, tib, cnt, refs, alpha, flags=flags3 | _record_flags(records, events))
     check(lib.pekf_device_sync())
-    return dict(ready=rb.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
-                refs=refs.download((K, 6), np.float64))
+    out = dict(ready=rb.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
+               refs=refs.download((K, 6), np.float64))
+    if calibration is not None:
+        out["calibrated"] = np.asarray(calibration["calibrated"], bool).copy()
+    return out
 
 
 def wire_events(frames, stream=None, frame_rows=False):
@@ -549,7 +588,7 @@ def wire_events(frames, stream=None, frame_rows=False):
                 first_t2=t2b, frames=fb)
 
 
-def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_rows=True):
+def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_rows=True, calibration=None):
     """A whole client session from the clients' wire frames, on the device end to end (KFS/Server.cpp's
     recv'd frames -> Parser.cpp:28-72): pekf_wire_events_ext_dev (the server's parse into FP64 event
     planes), pekf_frontend_init_ext_dev (phase 2) and pekf_live_ext_dev (phase 3 + the filter) on the
@@ -558,10 +597,14 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     wire_events), whose stores stay coalesced when the phones' phase-1 / phase-2 parts differ in length
     and whose frames a small batch splits over several waves; phase 2 and phase 3 read only the rows that
     hold messages (65,536 phones: 5.0 ms against 6.0 compacted with aligned rows, 5.0 against 8.0 ms with
-    rows 64 apart)."""
+    rows 64 apart).  calibration: as run_session (the phones' phase-1 frames are skipped by the device
+    parse: calibrate from wire.events_from_wire(texts, ..., phase=1))."""
     w = wire_events(frames, stream, frame_rows)
     K = filters.batch
     ib, tib, rb = DeviceBuffer(48 * K), DeviceBuffer(8 * K), DeviceBuffer(4 * K)
+    if calibration is not None:  # with frame rows the no-message rows are walked too (and left as they are)
+        _apply_calibration(calibration, K, w["E2"], w["ev2"].ptr, EV_F64_EVENTS, stream)
+        _apply_calibration(calibration, K, w["E3"], w["ev3"].ptr + 32 * K * w["ev3_from"], EV_F64_EVENTS, stream)
     check(lib.pekf_frontend_init_ext_dev(K, w["E2"], w["ev2"].ptr, w["first_t2"].ptr, int(n_avg), ib.ptr, tib.ptr,
                                          None, rb.ptr, EV_F64_EVENTS, stream))
     cnt, refs = DeviceBuffer(4 * K), DeviceBuffer(48 * K)
@@ -570,8 +613,11 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
         ev3 = types.SimpleNamespace(ptr=ev3.ptr + 32 * K * w["ev3_from"])
     filters.run_events_async(ev3, w["E3"], ib, tib, cnt, refs, alpha, stream, flags=EV_F64_EVENTS)
     check(lib.pekf_device_sync() if stream is None else lib.pekf_stream_sync(stream))
-    return dict(ready=rb.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
-                refs=refs.download((K, 6), np.float64))
+    out = dict(ready=rb.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
+               refs=refs.download((K, 6), np.float64))
+    if calibration is not None:
+        out["calibrated"] = np.asarray(calibration["calibrated"], bool).copy()
+    return out
 
 
 # ------------------------------------------------------------------ the batched filter

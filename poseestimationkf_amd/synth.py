@@ -395,6 +395,39 @@ def has_time_events(planes):
     return bool((np.ascontiguousarray(planes[..., 3]).view(np.uint32) == EV_TIME).any())
 
 
+# ---------------------------------------------------------------------------------------------
+# Phase-1 streams (the client's "Magnetometer Calibration" stage, ASC/SensorActivities.java:57-65):
+# magnetometer messages only, from a magnetometer with a soft- and hard-iron distortion.
+# ---------------------------------------------------------------------------------------------
+
+def soft_hard_iron(K, seed, soft=0.3, hard=40.0):
+    """K random distortions: (A (K, 3, 3) SPD soft-iron matrices with eigenvalues in [1 - soft, 1 + soft] on
+    random axes, h (K, 3) hard-iron offsets within +-hard).  A distorted sample is A @ m + h."""
+    rng = np.random.default_rng([int(seed), 0x1A])
+    q, _ = np.linalg.qr(rng.standard_normal((K, 3, 3)))
+    lam = 1.0 + soft * rng.uniform(-1.0, 1.0, (K, 3))
+    A = np.einsum("kij,kj,klj->kil", q, lam, q)
+    A = 0.5 * (A + A.transpose(0, 2, 1))
+    return A, rng.uniform(-hard, hard, (K, 3))
+
+
+def generate_calibration_events(K, n, seed=DEFAULT_SEED, field=B_UT, soft=0.3, hard=40.0, noise=0.05):
+    """Phase-1 streams of K phones in the engine's event-dict layout (host NumPy): n magnetometer messages
+    each (types all EV_MAG), gaps of about 10 ms.  The samples are a field of `field` units in directions
+    uniform over the sphere (the user turning the phone), through the phone's soft_hard_iron(K, seed, ...)
+    distortion, plus uniform noise of +-noise units, rounded to float32.  Returns dict(types (n, K) uint32,
+    values (n, K, 3) float32, times (n, K) int64, t_init (K,) int64, soft (K, 3, 3), hard (K, 3))."""
+    A, h = soft_hard_iron(K, seed, soft, hard)
+    rng = np.random.default_rng([int(seed), 0x1B])
+    u = rng.standard_normal((n, K, 3))
+    u /= np.linalg.norm(u, axis=2, keepdims=True)
+    m = field * np.einsum("kij,nkj->nki", A, u) + h[None] + rng.uniform(-noise, noise, (n, K, 3))
+    gaps = rng.integers(9_000_000, 11_000_001, (n, K))
+    t_init = np.full(K, T_INIT_NS, np.int64)
+    return dict(types=np.full((n, K), EV_MAG, np.uint32), values=m.astype(np.float32),
+                times=t_init[None, :] + np.cumsum(gaps, axis=0), t_init=t_init, soft=A, hard=h)
+
+
 def window_bytes(batch, window):
     return int(batch) * int(window) * 40
 
@@ -411,4 +444,5 @@ def c1_timestamps(dt_ns, t0_ns=1_234_567_890_123):
 
 __all__ = ["DEFAULT_SEED", "SynthParams", "Records", "philox4x32", "reference_vectors", "generate",
            "pack_planes", "unpack_planes", "refs_array", "window_bytes", "c1_timestamps",
-           "MISSING_BIT", "DT_MASK", "DT_ESCAPE", "pack_events", "pack_events64", "has_time_events", "EV_TIME", "EV_OTHER", "EV_NONE", "EV64_NONE_W"]
+           "MISSING_BIT", "DT_MASK", "DT_ESCAPE", "pack_events", "pack_events64", "has_time_events", "EV_TIME", "EV_OTHER", "EV_NONE", "EV64_NONE_W",
+           "soft_hard_iron", "generate_calibration_events"]

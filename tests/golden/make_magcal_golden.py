@@ -1,0 +1,90 @@
+"""Golden vectors for phase 1 (the magnetometer calibration), from the REFERENCE's own Python model of it
+(run in the survey container only):
+
+    PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/make_magcal_golden.py
+
+`MagnetometerCalibration_test.py` is the reference author's NumPy model of KFS/Magnetometer_Calibration.cpp:
+computeBias (:135-149) is setValues' running sum and division, compute_R (:120-132) the normal equations of
+setUncalibratedValues / LeastSquares_calculation solved with np.linalg.solve.  The module is imported by path
+(its __main__ block, which reads a data.csv, does not run) and the two functions are called unchanged on the
+streams of synth.generate_calibration_events; compute_R reads the module global number_of_elements, set here
+to the sample count.  No reference source is stored.
+
+Stored, for 48 phones x 101 samples (100 fitted + the message that fires the fit):
+  samples    (48, 101, 3) float32 -- the phones' magnetometer samples (exact: the streams are float32)
+  bias       (48, 3)  computeBias of the first 100 samples
+  fit        (48, 6)  compute_R's {a, b, c, d, e, f} of the first 100 samples minus bias
+  fit_exact  (48, 6)  the exact rational solution (fractions.Fraction) of the normal equations formed from
+                      the same float64 centred samples, rounded to float64 at the end
+  e_ref      ()       max over phones of max|fit - fit_exact| / max|fit_exact|: the reference's own error
+  w_ref      ()       max over phones of max|W W - R| / max|R| for W = NumPy's eigh-based root of compute_R's R
+
+Output: tests/golden/magcal.npz
+"""
+from __future__ import annotations
+
+import importlib.util
+import os
+import sys
+from fractions import Fraction
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+OUT = os.environ.get("PEKF_GOLDEN_OUT") or HERE
+ROOT = os.path.dirname(os.path.dirname(HERE))
+REF_FILE = "/root/reference/MagnetometerCalibration_test.py"
+sys.path.insert(0, ROOT)
+sys.dont_write_bytecode = True
+os.environ.setdefault("MPLBACKEND", "Agg")
+
+from poseestimationkf_amd import synth  # noqa: E402
+
+K, N_CAL, SEED = 48, 100, 20240519
+
+
+def exact_fit(v):
+    """The exact solution of (A^T A) x = A^T 1 for the design rows of the float64 samples v (n, 3)."""
+    rows = []
+    for x, y, z in v:
+        x, y, z = Fraction(float(x)), Fraction(float(y)), Fraction(float(z))
+        rows.append([x * x, y * y, z * z, 2 * x * y, 2 * z * x, 2 * y * z])
+    M = [[sum(r[i] * r[j] for r in rows) for j in range(6)] + [sum(r[i] for r in rows)] for i in range(6)]
+    for c in range(6):  # Gauss-Jordan in rationals
+        p = next(r for r in range(c, 6) if M[r][c] != 0)
+        M[c], M[p] = M[p], M[c]
+        M[c] = [e / M[c][c] for e in M[c]]
+        for r in range(6):
+            if r != c and M[r][c] != 0:
+                M[r] = [a - M[r][c] * b for a, b in zip(M[r], M[c])]
+    return np.array([float(M[i][6]) for i in range(6)])
+
+
+def main():
+    spec = importlib.util.spec_from_file_location("pekf_ref_magcal", REF_FILE)
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    ref.number_of_elements = N_CAL
+    ev = synth.generate_calibration_events(K, N_CAL + 1, seed=SEED)
+    samples = np.ascontiguousarray(ev["values"].transpose(1, 0, 2))  # (K, 101, 3) float32
+    bias, fit, fit_exact = np.empty((K, 3)), np.empty((K, 6)), np.empty((K, 6))
+    e_ref = w_ref = 0.0
+    for k in range(K):
+        m = samples[k, :N_CAL].astype(np.float64)
+        bias[k] = ref.computeBias(m, N_CAL)
+        v = m - np.asarray(bias[k])
+        R = ref.compute_R(v)
+        fit[k] = [R[0, 0], R[1, 1], R[2, 2], R[0, 1], R[0, 2], R[1, 2]]
+        fit_exact[k] = exact_fit(v)
+        e_ref = max(e_ref, float(np.abs(fit[k] - fit_exact[k]).max() / np.abs(fit_exact[k]).max()))
+        lam, V = np.linalg.eigh(R)
+        W = (V * np.sqrt(lam)) @ V.T
+        w_ref = max(w_ref, float(np.abs(W @ W - R).max() / np.abs(R).max()))
+    path = os.path.join(OUT, "magcal.npz")
+    np.savez_compressed(path, samples=samples, bias=bias, fit=fit, fit_exact=fit_exact,
+                        e_ref=np.float64(e_ref), w_ref=np.float64(w_ref))
+    print("magcal.npz %d bytes, e_ref %.3e, w_ref %.3e" % (os.path.getsize(path), e_ref, w_ref))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,343 @@
+"""Phase 1 on the device (csrc/pekf_magcal.hip: pekf_magcal_dev, pekf_magcal_apply_dev; engine.calibrate_magnetometer,
+run_session / run_wire_session with a calibration) against the reference's own results (tests/golden/magcal.npz),
+the NumPy restatement (tests/magcal_numpy.py) and the oracle chain.
+
+Shapes: batch 200 (three full waves and a partial one), planes of 104 rows and more (a last block of the 8-row
+event ring that needs padding)."""
+import os
+
+import numpy as np
+import pytest
+
+from poseestimationkf_amd import synth, wire
+
+from . import magcal_numpy as mc
+from .conftest import GOLDEN
+from .test_magcal_cpu import hyperboloid_samples
+
+pytestmark = pytest.mark.gpu
+
+K = 200
+N_CAL = 100
+EPS = float(np.finfo(np.float64).eps)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from poseestimationkf_amd import engine
+    from poseestimationkf_amd._lib import device_count
+    assert device_count() > 0, "GPU tests need a HIP device"
+    return engine
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with np.load(os.path.join(GOLDEN, "magcal.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _with_values64(ev):
+    """The FP64 event form carries the same (float32-exact) samples, not the server's parse of their text."""
+    return dict(ev, values64=np.asarray(ev["values"], np.float64))
+
+
+def _pad_rows(ev, rows):
+    """An event dict padded to `rows` rows with no-message entries (synth.EV_NONE)."""
+    E, Kk = ev["types"].shape
+    n = rows - E
+    return dict(ev, types=np.concatenate([ev["types"], np.full((n, Kk), synth.EV_NONE, np.uint32)]),
+                values=np.concatenate([ev["values"], np.zeros((n, Kk, 3), np.float32)]),
+                times=np.concatenate([ev["times"], np.repeat(ev["times"][-1:], n, axis=0)]))
+
+
+@pytest.fixture(scope="module")
+def base(golden):
+    """200 phones x 101 messages in 104 rows: phones 0-47 the fixture's, the rest generated."""
+    ev = synth.generate_calibration_events(K, N_CAL + 1, seed=77)
+    vals = ev["values"].copy()
+    vals[:, :48] = golden["samples"].transpose(1, 0, 2)
+    return _with_values64(_pad_rows(dict(ev, values=vals), 104))
+
+
+@pytest.fixture(scope="module")
+def base_cal(eng, base):
+    """The device's calibration of `base` with each event form (shared, not modified)."""
+    return {form: eng.calibrate_magnetometer(base, n_cal=N_CAL, events=form) for form in ("f32", "f64")}
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+@pytest.mark.parametrize("events", ["f32", "f64"])
+def test_magcal_fixture_parity(eng, golden, base, base_cal, events):
+    """bias bit for bit the reference's computeBias (every phone: the restatement's, the same sequence of
+    operations); fit within 8 e_ref of the exact rational solution; W symmetric bit for bit and W W - R within
+    8 w_ref (R of the device's own fit).  The f32 planes hold the same samples exactly, so the same checks hold.
+    Measured on MI355X (both forms): fit 2.05e-15 from the exact solution (e_ref 2.01e-15, the bound 1.61e-14; the
+    NumPy restatement 2.16e-15), root residual 2.02e-15 (w_ref 3.88e-15, the bound 3.10e-14), fit 1.43e-15 from
+    the restatement over the 200 phones."""
+    got = base_cal[events]
+    assert np.all(got["status"] == 0) and got["calibrated"].all()
+    assert np.array_equal(_bits(got["bias"][:48]), _bits(golden["bias"]))
+    model = mc.calibrate(base["types"], base["values"], n_cal=N_CAL)
+    assert np.array_equal(_bits(got["bias"]), _bits(model["bias"]))
+    e = mc.fit_error(got["fit"][:48], golden["fit_exact"]).max()
+    w = mc.root_residual(got["W"], mc.r_of(got["fit"])).max()
+    em = mc.fit_error(got["fit"], model["fit"]).max()
+    print("k_magcal (%s events): fit error vs exact %.3e (8 e_ref = %.3e), root residual %.3e (8 w_ref = %.3e), "
+          "fit vs the restatement over 200 phones %.3e" % (events, e, 8 * golden["e_ref"], w, 8 * golden["w_ref"], em))
+    assert e <= 8 * golden["e_ref"]
+    assert np.array_equal(_bits(got["W"]), _bits(got["W"].transpose(0, 2, 1)))
+    assert w <= 8 * golden["w_ref"]
+    # both within 8 e_ref of the exact solution, so within 16 e_ref of each other
+    assert em <= 16 * golden["e_ref"]
+    # cal (device) is what the dict holds
+    c = got["cal"].download((K, 12), np.float64)
+    assert np.array_equal(c[:, :3], got["bias"]) and np.array_equal(c[:, 3:].reshape(K, 3, 3), got["W"])
+
+
+def test_magcal_event_forms_agree(base_cal):
+    """The f32 and FP64 planes hold the same numbers, and the kernel's arithmetic is the same code: equal bits."""
+    a, b = base_cal["f32"], base_cal["f64"]
+    for key in ("bias", "W", "fit", "status"):
+        assert np.array_equal(a[key], b[key]), key
+
+
+def _ragged():
+    """Phones in groups of four, over 171 rows with no-message rows scattered in: 100 messages (not
+    calibrated), 150 messages, the same phone's first 101 only, and 101 messages of every type 0..3."""
+    rng = np.random.default_rng(91)
+    E = 171
+    src = synth.generate_calibration_events(K, 150, seed=78)
+    types = np.full((E, K), synth.EV_NONE, np.uint32)
+    vals = np.zeros((E, K, 3), np.float32)
+    times = np.zeros((E, K), np.int64)
+    n_msg = np.empty(K, np.int64)
+    for k in range(K):
+        kind = k % 4
+        n = (100, 150, 101, 101)[kind]
+        s = k - 1 if kind == 2 else k                          # kind 2: the stream of the phone before it
+        if kind == 2:
+            rows = np.nonzero(types[:, k - 1] != synth.EV_NONE)[0][:n]   # at the same rows
+        else:
+            rows = np.sort(rng.choice(E, n, replace=False))
+        types[rows, k] = synth.EV_MAG if kind != 3 else rng.integers(0, 4, n)
+        vals[rows, k] = src["values"][:n, s]
+        n_msg[k] = n
+        t = src["t_init"][k] + 10_000_000 * (1 + np.arange(E))
+        times[:, k] = t
+    return dict(types=types, values=vals, values64=vals.astype(np.float64), times=times,
+                t_init=src["t_init"]), n_msg
+
+
+@pytest.mark.parametrize("events", ["f32", "f64"])
+def test_magcal_ragged_streams_and_the_message_rule(eng, golden, events):
+    """The fit fires on message n_cal + 1 (Magnetometer_Calibration.cpp:18-25): 100 messages -> status 1, 101
+    -> 0, and 150 give the cal of their first 101.  Time events (f32 form: the no-message entries, and the
+    ones type-3 messages at awkward gaps need) and no-message rows (FP64 form) are not messages; messages of
+    type 0, 1 and 3 are samples like any other (Parser.cpp:30-34,144-147)."""
+    ev, n_msg = _ragged()
+    got = eng.calibrate_magnetometer(ev, n_cal=N_CAL, events=events)
+    assert np.array_equal(got["status"], np.where(n_msg <= N_CAL, 1, 0))
+    model = mc.calibrate(ev["types"], ev["values"], n_cal=N_CAL)
+    assert np.array_equal(got["status"], model["status"])
+    assert np.array_equal(_bits(got["bias"]), _bits(model["bias"]))   # the samples taken are the server's
+    ok = got["status"] == 0
+    assert np.array_equal(got["calibrated"], ok)
+    # device and restatement each within 8 e_ref of the exact solution (streams of the fixture's generator)
+    assert mc.fit_error(got["fit"][ok], model["fit"][ok]).max() <= 16 * golden["e_ref"]
+    long, first = np.arange(1, K, 4), np.arange(2, K, 4)
+    for key in ("bias", "W", "fit"):
+        assert np.array_equal(_bits(got[key][long]), _bits(got[key][first])), key
+    bad = ~ok
+    assert np.all(got["bias"][bad] == 0.0) and np.all(got["W"][bad] == np.eye(3)) and np.isnan(got["fit"][bad]).all()
+    assert np.isfinite(got["W"]).all() and np.isfinite(got["fit"][ok]).all()
+
+
+@pytest.mark.parametrize("events", ["f32", "f64"])
+def test_magcal_degenerate_phones(eng, base, base_cal, events):
+    """Exact by construction: 101 identical samples (dyadic values: every partial sum and the mean are exact,
+    the centred samples 0) and samples with z = 17.0 throughout (centred z exactly 0: a zero pivot) -> status 2;
+    +-h_i interleaved on the hyperboloid x^2 + y^2 - z^2 = 30^2 (mean exactly 0, fit (1, 1, -1) / 900) ->
+    status 3.  Every output is finite or as specified, and the other lanes' results do not change."""
+    vals = base["values"].copy()
+    flat, still, hyper = 5, 70, 130
+    vals[:101, flat, 2] = 17.0
+    vals[:101, still] = [12.5, -3.25, 40.0]
+    vals[:101, hyper] = hyperboloid_samples(101)
+    ev = _with_values64(dict(base, values=vals))
+    got = eng.calibrate_magnetometer(ev, n_cal=N_CAL, events=events)
+    want = np.zeros(K, np.int32)
+    want[[flat, still]] = 2
+    want[hyper] = 3
+    assert np.array_equal(got["status"], want)
+    bad = want != 0
+    assert np.all(got["bias"][bad] == 0.0) and np.all(got["W"][bad] == np.eye(3)) and np.isnan(got["fit"][bad]).all()
+    ref = base_cal[events]
+    for key in ("bias", "W", "fit"):
+        assert np.isfinite(got[key][~bad]).all()
+        assert np.array_equal(_bits(got[key][~bad]), _bits(ref[key][~bad])), key
+    assert np.array_equal(got["status"], mc.calibrate(ev["types"], vals, n_cal=N_CAL)["status"])
+
+
+def _mixed_plane():
+    """107 rows x 200 phones of mixed events (acc / gyro / mag, messages no sensor takes, no-message entries),
+    some magnetometer samples -0.0; a calibration with a third of the phones not calibrated."""
+    rng = np.random.default_rng(92)
+    E = 107
+    ev = synth.generate_events(np.arange(K), E, seed=79)
+    types = ev["types"].copy()
+    r = rng.random((E, K))
+    types[r < 0.05] = synth.EV_OTHER
+    types[r > 0.95] = synth.EV_NONE
+    vals = ev["values"].copy()
+    vals[rng.random((E, K)) < 0.05] = np.float32(-0.0)
+    A, h = synth.soft_hard_iron(K, 80)
+    W = np.linalg.inv(A) / synth.B_UT
+    W = 0.5 * (W + W.transpose(0, 2, 1))
+    status = ((np.arange(K) % 3 == 1) * (1 + np.arange(K) % 3)).astype(np.int32)
+    return dict(ev, types=types, values=vals), h, W, status
+
+
+@pytest.mark.parametrize("events", ["f32", "f64"])
+@pytest.mark.parametrize("with_status", [True, False])
+def test_magcal_apply(eng, events, with_status):
+    """In place on a plane of mixed events (107 rows: two row chunks, the last one cut short): the type-2 events
+    of calibrated phones are W (m - b) -- FP64: within 4 eps sum_j |W_ij| |m_j - b_j| per component of the
+    products' exact sum (three products and two adds, with or without fma, after the one rounded subtraction both
+    share); f32: within 1 f32 ulp of that value rounded -- and every other event, and every column whose status
+    != 0, keeps its bits (-0.0 included).  status NULL: every phone is corrected."""
+    from poseestimationkf_amd._lib import EV_F64_EVENTS, check, lib
+    ev, b, W, status = _mixed_plane()
+    if events == "f64":
+        planes = synth.pack_events64(ev, wire.server_values(ev["values"]))
+    else:
+        planes = synth.pack_events(ev)
+    E = planes.shape[0]
+    buf = eng.DeviceBuffer(planes.nbytes).upload(planes)
+    cal = eng.DeviceBuffer(96 * K).upload(np.concatenate([b, W.reshape(K, 9)], axis=1))
+    st = eng.DeviceBuffer(4 * K).upload(status)
+    check(lib.pekf_magcal_apply_dev(K, E, buf.ptr, cal.ptr, st.ptr if with_status else None,
+                                    EV_F64_EVENTS if events == "f64" else 0, None))
+    check(lib.pekf_device_sync())
+    out = buf.download(planes.shape, planes.dtype)
+    if events == "f64":
+        word = _bits(planes[..., 3])
+        is_mag = ((word & np.uint64(3)) == 2) & (word != np.uint64(synth.EV64_NONE_W))
+        as_bits = _bits
+    else:
+        word = np.ascontiguousarray(planes[..., 3]).view(np.uint32)
+        is_mag = (word & np.uint32(3)) == 2
+        as_bits = lambda a: np.ascontiguousarray(a).view(np.uint32)  # noqa: E731
+    sel = is_mag & ((status == 0)[None, :] if with_status else True)
+    assert sel.sum() > 1000 and (~sel & is_mag).sum() > (500 if with_status else -1)
+    keep = np.broadcast_to(~sel[..., None], planes.shape).copy()
+    keep[..., 3] = True
+    assert np.array_equal(as_bits(out)[keep], as_bits(planes)[keep])
+    with np.errstate(invalid="ignore"):                              # time events hold clock bits, not samples
+        d = np.where(sel[..., None], planes[..., :3].astype(np.float64) - b[None], 0.0)   # the kernel's rounded m - b
+    exact = np.einsum("kij,ekj->eki", W.astype(np.longdouble), d.astype(np.longdouble))
+    bound = 4 * EPS * np.einsum("kij,ekj->eki", np.abs(W), np.abs(d))
+    if events == "f64":
+        err = np.abs(out[..., :3].astype(np.longdouble) - exact)[sel]
+        print("k_magcal_apply (f64): worst error / bound %.3f" % float((err / bound[sel]).max()))
+        assert np.all(err <= bound[sel])
+    else:
+        want = exact.astype(np.float64).astype(np.float32)
+        ulp = np.spacing(np.abs(want))
+        err = np.abs(out[..., :3].astype(np.float64) - want.astype(np.float64))[sel]
+        print("k_magcal_apply (f32): worst error %.3f ulp" % float((err / ulp[sel]).max()))
+        assert np.all(err <= ulp[sel])
+
+
+ATOL_F64_CHAIN = 1e-12  # tests/test_live.py's bound for FP64 events against the oracle chain
+
+
+@pytest.fixture(scope="module")
+def session(eng):
+    """64 phones with a soft- and hard-iron distortion in all three phases; the device's calibration of phase 1."""
+    Ks = 64
+    ph1 = synth.generate_calibration_events(Ks, N_CAL + 1, seed=81)
+    A, h = ph1["soft"], ph1["hard"]
+    ph2 = synth.generate_events(np.arange(Ks), 700, seed=82)
+    ph3 = synth.generate_events(np.arange(Ks), 300, seed=83)
+    t1 = ph1["times"][-1]
+    ph2 = dict(ph2, times=ph2["times"] - ph2["t_init"][None, :] + t1[None, :], t_init=t1)
+    ph3 = dict(ph3, times=ph3["times"] - ph3["t_init"][None, :] + ph2["times"][-1][None, :])
+    for ph in (ph2, ph3):   # what the distorted magnetometer reports
+        m = np.einsum("kij,ekj->eki", A, ph["values"].astype(np.float64)) + h[None]
+        ph["values"] = np.where((ph["types"] == synth.EV_MAG)[..., None], m.astype(np.float32), ph["values"])
+    # phone 7 stops after 100 calibration messages: not calibrated, its samples stay raw
+    ph1["types"][N_CAL, 7] = synth.EV_NONE
+    calib = eng.calibrate_magnetometer(ph1, n_cal=N_CAL, events="f64")
+    return dict(K=Ks, ph1=ph1, ph2=ph2, ph3=ph3, calib=calib)
+
+
+def test_session_with_calibration_vs_oracle_chain(eng, session):
+    """run_session(calibration=...) with FP64 events against the oracle front-end chain (phase 2, phase 3) and
+    the reference filter's restatement, fed events corrected on the host with the device's cal -- the reference's
+    Parser.cpp:107 placement, equal to :239's up to rounding."""
+    from oracle import ekf_numpy
+    from oracle import frontend_numpy as fe
+    Ks, ph2, ph3, calib = session["K"], session["ph2"], session["ph3"], session["calib"]
+    assert calib["status"].tolist() == [1 if k == 7 else 0 for k in range(Ks)]
+    f = eng.BatchedEKF(Ks)
+    got = eng.run_session(ph2, ph3, f, events="f64", calibration=calib)
+    assert np.array_equal(got["calibrated"], calib["calibrated"]) and got["ready"].all()
+    X, _ = f.get_state()
+    v2 = mc.apply(wire.server_values(ph2["values"]), ph2["types"], calib["bias"], calib["W"], calib["status"])
+    v3 = mc.apply(wire.server_values(ph3["values"]), ph3["types"], calib["bias"], calib["W"], calib["status"])
+    worst = 0.0
+    for k in (0, 7, 13, 31, 63):
+        o = fe.initial_values(ph2["types"][:, k], v2[:, k], ph2["times"][:, k])
+        g, dt, a, m = fe.run_frontend(ph3["types"][:, k], v3[:, k], ph3["times"][:, k], o["acc"], o["mag"], o["t_init"])
+        assert got["counts"][k] == len(dt) > 0
+        Xo, _, _ = ekf_numpy.run_filter(g, dt.astype(np.float64), a, m, got["refs"][k, :3], got["refs"][k, 3:],
+                                        record=False)
+        worst = max(worst, float(np.abs(X[k] - Xo).max()))
+    print("session with calibration vs the oracle chain on host-corrected events: %.3e" % worst)
+    assert worst < ATOL_F64_CHAIN
+    # the correction matters: without it the same phones end elsewhere
+    f0 = eng.BatchedEKF(Ks)
+    eng.run_session(ph2, ph3, f0, events="f64")
+    X0, _ = f0.get_state()
+    assert np.abs(X0 - X).max(axis=1)[calib["calibrated"]].min() > 1e-6
+    assert np.array_equal(X0[7], X[7])                      # the uncalibrated phone's session is unchanged
+
+
+@pytest.fixture(scope="module")
+def session_texts(session):
+    """The session's three phases as each phone's wire text (phase-3 parts of different lengths)."""
+    Ks, ph1, ph2, ph3 = (session[k] for k in ("K", "ph1", "ph2", "ph3"))
+    texts = []
+    for k in range(Ks):
+        n1 = int((ph1["types"][:, k] != synth.EV_NONE).sum())
+        n3 = 300 - 7 * (k % 4)
+        texts.append(wire.events_text(ph1["types"][:n1, k], ph1["values"][:n1, k], ph1["times"][:n1, k], phase=1) +
+                     wire.events_text(ph2["types"][:, k], ph2["values"][:, k], ph2["times"][:, k], phase=2) +
+                     wire.events_text(ph3["types"][:n3, k], ph3["values"][:n3, k], ph3["times"][:n3, k], phase=3))
+    return texts
+
+
+@pytest.mark.parametrize("frame_rows", [True, False])
+def test_wire_session_with_calibration_equals_run_session(eng, session, session_texts, frame_rows):
+    """The same phones' frames through run_wire_session(calibration=...): the dict and the state run_session gives
+    on the host's parse of the same text, bit for bit (with frame rows the correction walks the no-message rows)."""
+    Ks, ph1, ph2, calib, texts = session["K"], session["ph1"], session["ph2"], session["calib"], session_texts
+    # phase 1 from the same text on the host: the calibration of the server's parsed values
+    e1 = wire.events_from_wire(texts, np.zeros((Ks, 3)), np.zeros((Ks, 3)), ph1["t_init"], phase=1)
+    cal_w = eng.calibrate_magnetometer(e1, n_cal=N_CAL, events="f64")
+    assert np.array_equal(cal_w["status"], calib["status"])
+    f_dev, f_host = eng.BatchedEKF(Ks), eng.BatchedEKF(Ks)
+    out_dev = eng.run_wire_session(wire.frames(texts), f_dev, frame_rows=frame_rows, calibration=cal_w)
+    t0 = ph2["times"][0]
+    e2 = wire.events_from_wire(texts, np.zeros((Ks, 3)), np.zeros((Ks, 3)), t0, phase=2)
+    e3 = wire.events_from_wire(texts, np.zeros((Ks, 3)), np.zeros((Ks, 3)), t0, phase=3)
+    out_host = eng.run_session(e2, e3, f_host, events="f64", calibration=cal_w)
+    assert sorted(out_dev) == sorted(out_host) == ["calibrated", "counts", "ready", "refs"]
+    assert out_dev["ready"].all() and out_dev["counts"].min() > 0
+    for key in out_dev:
+        assert np.array_equal(out_dev[key], out_host[key]), key
+    for a, b in zip(f_dev.get_state(), f_host.get_state()):
+        assert np.array_equal(a, b)
