@@ -394,15 +394,14 @@ extern "C" int pekf_frontend_init_ext_dev(int64_t batch, int64_t n_events, const
     PEKF_CHECK_ARG(ev_planes && t_start && init && t_init && ready, "null pointer");
     PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
     const dim3 grid(grid_for(batch, kFeBlock)), block(kFeBlock);
-    if (flags & PEKF_EV_F64_EVENTS)
-        hipLaunchKernelGGL(k_frontend_init<true>, grid, block, 0, as_stream(stream), batch, n_events,
-                           static_cast<const double4 *>(ev_planes), t_start, n_avg, init, t_init, stats, ready);
-    else  // phase 2 always honours time events
-        hipLaunchKernelGGL(k_frontend_init<false>, grid, block, 0, as_stream(stream), batch, n_events,
-                           static_cast<const float4 *>(ev_planes), t_start, n_avg, init, t_init, stats, ready);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_frontend_init");
-    return PEKF_OK;
+    dispatch_bools(
+        [&](auto ev64) {  // phase 2 always honours time events
+            using Ev = std::conditional_t<ev64.value, double4, float4>;
+            hipLaunchKernelGGL(k_frontend_init<ev64.value>, grid, block, 0, as_stream(stream), batch, n_events,
+                               static_cast<const Ev *>(ev_planes), t_start, n_avg, init, t_init, stats, ready);
+        },
+        (flags & PEKF_EV_F64_EVENTS) != 0);
+    return launched("k_frontend_init");
 }
 
 extern "C" int pekf_frontend_init_dev(int64_t batch, int64_t n_events, const void *ev_planes, const int64_t *t_start,
@@ -430,24 +429,18 @@ extern "C" int pekf_frontend_ext_dev(int64_t batch, int64_t n_events, const void
                        (uintptr_t)plane_my % 8 == 0,
                    "misaligned planes");
     const dim3 grid(grid_for(batch, 64)), block(64);
-    if (ev64)
-        hipLaunchKernelGGL((k_frontend<false, true>), grid, block, 0, as_stream(stream), batch, n_events,
-                           static_cast<const double4 *>(ev_planes), init, t_init, alpha, r_max,
-                           static_cast<double4 *>(plane_gd), static_cast<double4 *>(plane_am),
-                           static_cast<double2 *>(plane_my), nullptr, counts, refs, dev_error);
-    else if (flags & PEKF_EV_TIME_EVENTS)
-        hipLaunchKernelGGL(k_frontend<true>, grid, block, 0, as_stream(stream), batch, n_events,
-                           static_cast<const float4 *>(ev_planes), init, t_init, alpha, r_max,
-                           static_cast<float4 *>(plane_gd), static_cast<float4 *>(plane_am),
-                           static_cast<float2 *>(plane_my), dt_ext, counts, refs, dev_error);
+    auto launch = [&](auto te, auto e64) {  // FP64 events: FP64 planes, and dt_ext is null (checked above)
+        using V4 = std::conditional_t<e64.value, double4, float4>;
+        using V2 = std::conditional_t<e64.value, double2, float2>;
+        hipLaunchKernelGGL((k_frontend<te.value, e64.value>), grid, block, 0, as_stream(stream), batch, n_events,
+                           static_cast<const V4 *>(ev_planes), init, t_init, alpha, r_max, static_cast<V4 *>(plane_gd),
+                           static_cast<V4 *>(plane_am), static_cast<V2 *>(plane_my), dt_ext, counts, refs, dev_error);
+    };
+    if (ev64)  // the one FP64-event variant
+        launch(std::false_type{}, std::true_type{});
     else
-        hipLaunchKernelGGL(k_frontend<false>, grid, block, 0, as_stream(stream), batch, n_events,
-                           static_cast<const float4 *>(ev_planes), init, t_init, alpha, r_max,
-                           static_cast<float4 *>(plane_gd), static_cast<float4 *>(plane_am),
-                           static_cast<float2 *>(plane_my), dt_ext, counts, refs, dev_error);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_frontend");
-    return PEKF_OK;
+        dispatch_bools([&](auto te) { launch(te, std::false_type{}); }, (flags & PEKF_EV_TIME_EVENTS) != 0);
+    return launched("k_frontend");
 }
 
 extern "C" int pekf_frontend_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,

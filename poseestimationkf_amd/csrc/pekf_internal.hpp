@@ -7,6 +7,9 @@
 #include <cstddef>
 #include <cstdint>
 #include <initializer_list>
+#include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "../../include/pekf.h"
 
@@ -26,6 +29,22 @@ int require_device();
     do {                                                                 \
         if (!(cond)) return ::pekf::set_error(PEKF_ERR_INVALID, "%s", msg); \
     } while (0)
+
+// After hipLaunchKernelGGL: the launch's error, if any, reported under the kernel's name.
+// (static, like staged_call below: the library's exported symbols stay those of the C ABI and its plumbing)
+static inline int launched(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, what);
+    return PEKF_OK;
+}
+
+// Run-time flags to template flags: calls f(std::bool_constant<b>{}...), so a generic lambda states a
+// launch once and picks the kernel variant with <a.value, b.value, ...>.  Every combination is instantiated.
+template <class F> inline void dispatch_bools(F &&f) { f(); }
+template <class F, class... Bs> inline void dispatch_bools(F &&f, bool b, Bs... rest) {
+    if (b) dispatch_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else   dispatch_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -103,6 +122,61 @@ class Staging {
     bool zero_copy_ = false;
     int device_ = -1;
 };
+
+// One host-pointer operator call: kernel(n, inputs..., outputs..., [status plane,] Done) over n items.
+// An operand is its host pointer and its doubles per item.  ONE is the operator's n = 1 route (call1<OP>
+// of pekf_percall.hip) or nullptr; ERR is the code a non-zero entry of the kernel's status plane maps to,
+// with err_msg, or PEKF_OK for a kernel without a status plane.  The caller has checked its arguments.
+struct OpIn {
+    const double *ptr;
+    size_t width;
+};
+struct OpOut {
+    double *ptr;
+    size_t width;
+};
+using Call1Fn = int (*)(std::initializer_list<HostArg>, std::initializer_list<HostOut>, int32_t *);
+
+template <int BLOCK, Call1Fn ONE, int ERR, class K, size_t NI, size_t NO, size_t... I, size_t... O>
+static int staged_call(K kernel, const char *name, int64_t n, const OpIn (&in)[NI], const OpOut (&out)[NO],
+                       const char *err_msg, std::index_sequence<I...>, std::index_sequence<O...>) {
+    constexpr bool kStatus = ERR != PEKF_OK;
+    if (int st = require_device()) return st;
+    const size_t b = (size_t)n * sizeof(double);
+    if constexpr (ONE != nullptr) {
+        if (n == 1) {
+            int32_t st1 = 0;
+            if (int st = ONE({{in[I].ptr, in[I].width * b}...}, {{out[O].ptr, out[O].width * b}...}, &st1)) return st;
+            return kStatus && st1 ? set_error(ERR, "%s", err_msg) : PEKF_OK;
+        }
+    }
+    Staging &s = Staging::get();
+    // the status plane follows the outputs; without one it is an empty plane that nothing reads or writes
+    std::vector<int32_t> status(kStatus ? (size_t)n : 0);
+    const size_t sb = status.size() * sizeof(int32_t);
+    void *din[NI], *dout[NO + 1];
+    if (int st = s.stage_in({{in[I].ptr, in[I].width * b}...}, {out[O].width * b..., sb}, din, dout)) return st;
+    auto launch = [&](auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s.stream(), n,
+                           static_cast<const double *>(din[I])..., static_cast<double *>(dout[O])..., tail...);
+    };
+    if constexpr (kStatus)
+        launch(static_cast<int32_t *>(dout[NO]), s.done(grid_for(n, BLOCK)));
+    else
+        launch(s.done(grid_for(n, BLOCK)));
+    if (int st = launched(name)) return st;
+    if (int st = s.stage_out({{out[O].ptr, out[O].width * b}..., {status.data(), sb}}, dout)) return st;
+    for (int32_t v : status)
+        if (v) return set_error(ERR, "%s", err_msg);
+    return PEKF_OK;
+}
+
+template <int BLOCK, Call1Fn ONE = nullptr, int ERR = PEKF_OK, class K, size_t NI, size_t NO>
+static int staged_call(K kernel, const char *name, int64_t n, const OpIn (&in)[NI], const OpOut (&out)[NO],
+                       const char *err_msg = nullptr) {
+    return staged_call<BLOCK, ONE, ERR>(kernel, name, n, in, out, err_msg, std::make_index_sequence<NI>{},
+                                        std::make_index_sequence<NO>{});
+}
 
 // Stops the resident per-call service kernel (pekf_percall.hip) of every device, e.g. before a
 // device-wide synchronisation, which would otherwise wait for its idle limit.

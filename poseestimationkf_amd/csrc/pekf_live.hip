@@ -421,23 +421,18 @@ extern "C" int pekf_live_ext_dev(int64_t batch, int64_t n_events, const void *ev
     PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
     PEKF_CHECK_ARG(r > 0.0, "r must be > 0 (S = P- + rI must be SPD)");
     (void)dev_error;  // every record's dt is applied (escaped ones from the queue's side entries)
-    const auto *ev = static_cast<const float4 *>(ev_planes);
     const dim3 grid(grid_for(batch, kRunBlock)), block(kRunBlock);
-    const bool te = (flags & PEKF_EV_TIME_EVENTS) != 0, r64 = (flags & PEKF_EV_F32_RECORDS) == 0;
-    auto launch = [&](auto kernel) {
+    auto launch = [&](auto kernel, const auto *ev) {
         hipLaunchKernelGGL(kernel, grid, block, 0, as_stream(stream), batch, n_events, ev, init, t_init, alpha, q, r, X,
                            P, counts, refs);
     };
-    if (ev64)
-        hipLaunchKernelGGL((k_live<false, false, true>), grid, block, 0, as_stream(stream), batch, n_events,
-                           static_cast<const double4 *>(ev_planes), init, t_init, alpha, q, r, X, P, counts, refs);
-    else if (te)
-        r64 ? launch(k_live<true, true>) : launch(k_live<true, false>);
+    if (ev64)  // the one FP64-event variant
+        launch(k_live<false, false, true>, static_cast<const double4 *>(ev_planes));
     else
-        r64 ? launch(k_live<false, true>) : launch(k_live<false, false>);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_live");
-    return PEKF_OK;
+        dispatch_bools(
+            [&](auto te, auto r64) { launch(k_live<te.value, r64.value>, static_cast<const float4 *>(ev_planes)); },
+            (flags & PEKF_EV_TIME_EVENTS) != 0, (flags & PEKF_EV_F32_RECORDS) == 0);
+    return launched("k_live");
 }
 
 extern "C" int pekf_live_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,

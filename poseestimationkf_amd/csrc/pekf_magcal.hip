@@ -284,15 +284,14 @@ extern "C" int pekf_magcal_dev(int64_t batch, int64_t n_events, const void *ev_p
     PEKF_CHECK_ARG(ev_planes && cal && status, "null pointer");
     PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
     const dim3 grid(grid_for(batch, kMcBlock)), block(kMcBlock);
-    if (flags & PEKF_EV_F64_EVENTS)
-        hipLaunchKernelGGL(k_magcal<true>, grid, block, 0, as_stream(stream), batch, n_events,
-                           static_cast<const double4 *>(ev_planes), n_cal, cal, fit, status);
-    else  // time events are always honoured, as in phase 2
-        hipLaunchKernelGGL(k_magcal<false>, grid, block, 0, as_stream(stream), batch, n_events,
-                           static_cast<const float4 *>(ev_planes), n_cal, cal, fit, status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_magcal");
-    return PEKF_OK;
+    dispatch_bools(
+        [&](auto ev64) {  // time events are always honoured, as in phase 2
+            using Ev = std::conditional_t<ev64.value, double4, float4>;
+            hipLaunchKernelGGL(k_magcal<ev64.value>, grid, block, 0, as_stream(stream), batch, n_events,
+                               static_cast<const Ev *>(ev_planes), n_cal, cal, fit, status);
+        },
+        (flags & PEKF_EV_F64_EVENTS) != 0);
+    return launched("k_magcal");
 }
 
 extern "C" int pekf_magcal_apply_dev(int64_t batch, int64_t n_events, void *ev_planes, const double *cal,
@@ -308,13 +307,12 @@ extern "C" int pekf_magcal_apply_dev(int64_t batch, int64_t n_events, void *ev_p
     if (chunks > 65535) chunks = 65535;
     const int64_t rows = (n_events + chunks - 1) / chunks;
     const dim3 grid(grid_for(batch, kMcBlock), (unsigned)chunks), block(kMcBlock);
-    if (flags & PEKF_EV_F64_EVENTS)
-        hipLaunchKernelGGL(k_magcal_apply<true>, grid, block, 0, as_stream(stream), batch, n_events, (int32_t)rows,
-                           static_cast<double4 *>(ev_planes), cal, status);
-    else
-        hipLaunchKernelGGL(k_magcal_apply<false>, grid, block, 0, as_stream(stream), batch, n_events, (int32_t)rows,
-                           static_cast<float4 *>(ev_planes), cal, status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_magcal_apply");
-    return PEKF_OK;
+    dispatch_bools(
+        [&](auto ev64) {
+            using Ev = std::conditional_t<ev64.value, double4, float4>;
+            hipLaunchKernelGGL(k_magcal_apply<ev64.value>, grid, block, 0, as_stream(stream), batch, n_events,
+                               (int32_t)rows, static_cast<Ev *>(ev_planes), cal, status);
+        },
+        (flags & PEKF_EV_F64_EVENTS) != 0);
+    return launched("k_magcal_apply");
 }

@@ -681,7 +681,7 @@ class Service {
 
     int launch() {
         hipLaunchKernelGGL(k_service, dim3(1), dim3(64), 0, stream_, box_dev_, idle_ticks_);
-        if (hipGetLastError() != hipSuccess) {
+        if (launched("k_service") != PEKF_OK) {  // its message is replaced below
             broken_ = true;
             return set_error(PEKF_ERR_HIP, "per-call service: launch failed");
         }
@@ -771,12 +771,6 @@ void Service::quiesce_all() {
 
 void service_quiesce_all() { Service::quiesce_all(); }
 
-static int launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what);
-    return PEKF_OK;
-}
-
 #define PEKF_GRID(n) dim3(grid_for((n), kBlock)), dim3(kBlock)
 
 // Host side of k_call1: packs the inputs (in order) into the Blob, runs the call with zero-copy
@@ -818,8 +812,6 @@ static int call1(std::initializer_list<HostArg> ins, std::initializer_list<HostO
     }
     return PEKF_OK;
 }
-
-#define D(T, p) static_cast<T>(p)
 
 }  // namespace pekf
 
@@ -879,21 +871,10 @@ int pekf_rk4(int64_t n, const double *q0, const double *dt_ns, const double *w, 
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(q0 && dt_ns && w && q_out, "null pointer");
-    if (int st = require_device()) return st;
-    if (n == 1) {
-        int32_t st1 = 0;
-        return call1<kCallRk4>({{q0, 32}, {dt_ns, 8}, {w, 24}}, {{q_out, 32}}, &st1);
-    }
-    Staging &s = Staging::get();
-    const size_t b = (size_t)n * sizeof(double);
-    void *in[3], *out[1];
-    if (int st = s.stage_in({{q0, 4 * b}, {dt_ns, b}, {w, 3 * b}}, {4 * b}, in, out)) return st;
-    hipLaunchKernelGGL(k_rk4, PEKF_GRID(n), 0, s.stream(), n, D(const double *, in[0]),
-                       D(const double *, in[1]), D(const double *, in[2]), D(double *, out[0]), s.done(grid_for(n, kBlock)));
-    if (int st = launched("k_rk4")) return st;
-    return s.stage_out({{q_out, 4 * b}}, out);
+    return staged_call<kBlock, call1<kCallRk4>>(k_rk4, "k_rk4", n, {{q0, 4}, {dt_ns, 1}, {w, 3}}, {{q_out, 4}});
 }
 
+// written out: k_norm takes len as well, and has no n = 1 route
 int pekf_norm(int64_t n, int64_t len, const double *a, double *res) {
     PEKF_CHECK_ARG(n >= 0 && len >= 0, "negative size");
     if (n == 0) return PEKF_OK;
@@ -903,8 +884,8 @@ int pekf_norm(int64_t n, int64_t len, const double *a, double *res) {
     const size_t b = (size_t)n * sizeof(double);
     void *in[1], *out[1];
     if (int st = s.stage_in({{a, (size_t)len * b}}, {b}, in, out)) return st;
-    hipLaunchKernelGGL(k_norm, PEKF_GRID(n), 0, s.stream(), n, len, D(const double *, in[0]),
-                       D(double *, out[0]), s.done(grid_for(n, kBlock)));
+    hipLaunchKernelGGL(k_norm, PEKF_GRID(n), 0, s.stream(), n, len, static_cast<const double *>(in[0]),
+                       static_cast<double *>(out[0]), s.done(grid_for(n, kBlock)));
     if (int st = launched("k_norm")) return st;
     return s.stage_out({{res, b}}, out);
 }
@@ -913,57 +894,22 @@ int pekf_jacobian_a(int64_t n, const double *w, double *A) {
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(w && A, "null pointer");
-    if (int st = require_device()) return st;
-    if (n == 1) {
-        int32_t st1 = 0;
-        return call1<kCallJacA>({{w, 24}}, {{A, 128}}, &st1);
-    }
-    Staging &s = Staging::get();
-    const size_t b = (size_t)n * sizeof(double);
-    void *in[1], *out[1];
-    if (int st = s.stage_in({{w, 3 * b}}, {16 * b}, in, out)) return st;
-    hipLaunchKernelGGL(k_jac_a, PEKF_GRID(n), 0, s.stream(), n, D(const double *, in[0]),
-                       D(double *, out[0]), s.done(grid_for(n, kBlock)));
-    if (int st = launched("k_jac_a")) return st;
-    return s.stage_out({{A, 16 * b}}, out);
+    return staged_call<kBlock, call1<kCallJacA>>(k_jac_a, "k_jac_a", n, {{w, 3}}, {{A, 16}});
 }
 
 int pekf_jacobian_b(int64_t n, const double *q, double *Jb) {
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(q && Jb, "null pointer");
-    if (int st = require_device()) return st;
-    if (n == 1) {
-        int32_t st1 = 0;
-        return call1<kCallJacB>({{q, 32}}, {{Jb, 96}}, &st1);
-    }
-    Staging &s = Staging::get();
-    const size_t b = (size_t)n * sizeof(double);
-    void *in[1], *out[1];
-    if (int st = s.stage_in({{q, 4 * b}}, {12 * b}, in, out)) return st;
-    hipLaunchKernelGGL(k_jac_b, PEKF_GRID(n), 0, s.stream(), n, D(const double *, in[0]),
-                       D(double *, out[0]), s.done(grid_for(n, kBlock)));
-    if (int st = launched("k_jac_b")) return st;
-    return s.stage_out({{Jb, 12 * b}}, out);
+    return staged_call<kBlock, call1<kCallJacB>>(k_jac_b, "k_jac_b", n, {{q, 4}}, {{Jb, 12}});
 }
 
 int pekf_comparator(int64_t n, const double *q1, const double *q2, double *res) {
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(q1 && q2 && res, "null pointer");
-    if (int st = require_device()) return st;
-    if (n == 1) {
-        int32_t st1 = 0;
-        return call1<kCallComparator>({{q1, 32}, {q2, 32}}, {{res, 32}}, &st1);
-    }
-    Staging &s = Staging::get();
-    const size_t b = (size_t)n * sizeof(double);
-    void *in[2], *out[1];
-    if (int st = s.stage_in({{q1, 4 * b}, {q2, 4 * b}}, {4 * b}, in, out)) return st;
-    hipLaunchKernelGGL(k_comparator, PEKF_GRID(n), 0, s.stream(), n, D(const double *, in[0]),
-                       D(const double *, in[1]), D(double *, out[0]), s.done(grid_for(n, kBlock)));
-    if (int st = launched("k_comparator")) return st;
-    return s.stage_out({{res, 4 * b}}, out);
+    return staged_call<kBlock, call1<kCallComparator>>(k_comparator, "k_comparator", n, {{q1, 4}, {q2, 4}},
+                                                       {{res, 4}});
 }
 
 int pekf_predict(int64_t n, const double *gyro, const double *dt_ns, const double *X,
@@ -972,31 +918,9 @@ int pekf_predict(int64_t n, const double *gyro, const double *dt_ns, const doubl
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(gyro && dt_ns && X && P && Q && R && z && Pm && K, "null pointer");
-    if (int st = require_device()) return st;
-    const size_t b = (size_t)n * sizeof(double);
-    if (n == 1) {
-        int32_t st1 = 0;
-        if (int st = call1<kCallPredict>({{gyro, 3 * b}, {dt_ns, b}, {X, 4 * b}, {P, 16 * b}, {Q, 9 * b}, {R, 16 * b}},
-                                         {{z, 4 * b}, {Pm, 16 * b}, {K, 16 * b}}, &st1))
-            return st;
-        return st1 ? set_error(PEKF_ERR_SINGULAR, "Singular matrix") : PEKF_OK;
-    }
-    Staging &s = Staging::get();
-    const size_t sb = (size_t)n * sizeof(int32_t);
-    std::vector<int32_t> status((size_t)n);
-    void *in[6], *out[4];
-    if (int st = s.stage_in({{gyro, 3 * b}, {dt_ns, b}, {X, 4 * b}, {P, 16 * b}, {Q, 9 * b}, {R, 16 * b}},
-                            {4 * b, 16 * b, 16 * b, sb}, in, out))
-        return st;
-    hipLaunchKernelGGL(k_predict, PEKF_GRID(n), 0, s.stream(), n, D(const double *, in[0]),
-                       D(const double *, in[1]), D(const double *, in[2]), D(const double *, in[3]),
-                       D(const double *, in[4]), D(const double *, in[5]), D(double *, out[0]),
-                       D(double *, out[1]), D(double *, out[2]), D(int32_t *, out[3]), s.done(grid_for(n, kBlock)));
-    if (int st = launched("k_predict")) return st;
-    if (int st = s.stage_out({{z, 4 * b}, {Pm, 16 * b}, {K, 16 * b}, {status.data(), sb}}, out)) return st;
-    for (int32_t v : status)
-        if (v) return set_error(PEKF_ERR_SINGULAR, "Singular matrix");
-    return PEKF_OK;
+    return staged_call<kBlock, call1<kCallPredict>, PEKF_ERR_SINGULAR>(
+        k_predict, "k_predict", n, {{gyro, 3}, {dt_ns, 1}, {X, 4}, {P, 16}, {Q, 9}, {R, 16}},
+        {{z, 4}, {Pm, 16}, {K, 16}}, "Singular matrix");
 }
 
 int pekf_correct(int64_t n, const double *mag, const double *acc, const double *z,
@@ -1005,33 +929,9 @@ int pekf_correct(int64_t n, const double *mag, const double *acc, const double *
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(mag && acc && z && P && K && acc0 && mag0 && X && P_out, "null pointer");
-    if (int st = require_device()) return st;
-    const size_t b = (size_t)n * sizeof(double);
-    if (n == 1) {
-        int32_t st1 = 0;
-        if (int st = call1<kCallCorrect>({{mag, 3 * b}, {acc, 3 * b}, {z, 4 * b}, {P, 16 * b}, {K, 16 * b},
-                                          {acc0, 3 * b}, {mag0, 3 * b}},
-                                         {{X, 4 * b}, {P_out, 16 * b}}, &st1))
-            return st;
-        return st1 ? set_error(PEKF_ERR_SVD, "SVD did not converge") : PEKF_OK;
-    }
-    Staging &s = Staging::get();
-    const size_t sb = (size_t)n * sizeof(int32_t);
-    std::vector<int32_t> status((size_t)n);
-    void *in[7], *out[3];
-    if (int st = s.stage_in({{mag, 3 * b}, {acc, 3 * b}, {z, 4 * b}, {P, 16 * b}, {K, 16 * b},
-                             {acc0, 3 * b}, {mag0, 3 * b}},
-                            {4 * b, 16 * b, sb}, in, out))
-        return st;
-    hipLaunchKernelGGL(k_correct, PEKF_GRID(n), 0, s.stream(), n, D(const double *, in[0]),
-                       D(const double *, in[1]), D(const double *, in[2]), D(const double *, in[3]),
-                       D(const double *, in[4]), D(const double *, in[5]), D(const double *, in[6]),
-                       D(double *, out[0]), D(double *, out[1]), D(int32_t *, out[2]), s.done(grid_for(n, kBlock)));
-    if (int st = launched("k_correct")) return st;
-    if (int st = s.stage_out({{X, 4 * b}, {P_out, 16 * b}, {status.data(), sb}}, out)) return st;
-    for (int32_t v : status)
-        if (v) return set_error(PEKF_ERR_SVD, "SVD did not converge");
-    return PEKF_OK;
+    return staged_call<kBlock, call1<kCallCorrect>, PEKF_ERR_SVD>(
+        k_correct, "k_correct", n, {{mag, 3}, {acc, 3}, {z, 4}, {P, 16}, {K, 16}, {acc0, 3}, {mag0, 3}},
+        {{X, 4}, {P_out, 16}}, "SVD did not converge");
 }
 
 static int wahba_host(bool quat, int64_t n, const double *acc0, const double *mag0,
@@ -1040,40 +940,11 @@ static int wahba_host(bool quat, int64_t n, const double *acc0, const double *ma
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(acc0 && mag0 && acc && mag && k_acc && k_mag && res, "null pointer");
-    if (int st = require_device()) return st;
-    const size_t b = (size_t)n * sizeof(double);
-    if (n == 1) {
-        int32_t st1 = 0;
-        const std::initializer_list<HostArg> ins = {{acc0, 3 * b}, {mag0, 3 * b}, {acc, 3 * b}, {mag, 3 * b},
-                                                    {k_acc, b}, {k_mag, b}};
-        const int st = quat ? call1<kCallWahbaQuat>(ins, {{res, 4 * b}}, &st1)
-                            : call1<kCallWahbaRot>(ins, {{res, 9 * b}}, &st1);
-        if (st) return st;
-        return st1 ? set_error(PEKF_ERR_SVD, "SVD did not converge") : PEKF_OK;
-    }
-    Staging &s = Staging::get();
-    const size_t ob = (quat ? 4 : 9) * b;
-    const size_t sb = (size_t)n * sizeof(int32_t);
-    std::vector<int32_t> status((size_t)n);
-    void *in[6], *out[2];
-    if (int st = s.stage_in({{acc0, 3 * b}, {mag0, 3 * b}, {acc, 3 * b}, {mag, 3 * b}, {k_acc, b}, {k_mag, b}},
-                            {ob, sb}, in, out))
-        return st;
-    if (quat)
-        hipLaunchKernelGGL(k_wahba<true>, PEKF_GRID(n), 0, s.stream(), n, D(const double *, in[0]),
-                           D(const double *, in[1]), D(const double *, in[2]), D(const double *, in[3]),
-                           D(const double *, in[4]), D(const double *, in[5]), D(double *, out[0]),
-                           D(int32_t *, out[1]), s.done(grid_for(n, kBlock)));
-    else
-        hipLaunchKernelGGL(k_wahba<false>, PEKF_GRID(n), 0, s.stream(), n, D(const double *, in[0]),
-                           D(const double *, in[1]), D(const double *, in[2]), D(const double *, in[3]),
-                           D(const double *, in[4]), D(const double *, in[5]), D(double *, out[0]),
-                           D(int32_t *, out[1]), s.done(grid_for(n, kBlock)));
-    if (int st = launched("k_wahba")) return st;
-    if (int st = s.stage_out({{res, ob}, {status.data(), sb}}, out)) return st;
-    for (int32_t v : status)
-        if (v) return set_error(PEKF_ERR_SVD, "SVD did not converge");
-    return PEKF_OK;
+    const OpIn ins[] = {{acc0, 3}, {mag0, 3}, {acc, 3}, {mag, 3}, {k_acc, 1}, {k_mag, 1}};
+    constexpr Call1Fn one_quat = call1<kCallWahbaQuat>, one_rot = call1<kCallWahbaRot>;
+    const char *err = "SVD did not converge";
+    if (quat) return staged_call<kBlock, one_quat, PEKF_ERR_SVD>(k_wahba<true>, "k_wahba", n, ins, {{res, 4}}, err);
+    return staged_call<kBlock, one_rot, PEKF_ERR_SVD>(k_wahba<false>, "k_wahba", n, ins, {{res, 9}}, err);
 }
 
 int pekf_wahba_rotation(int64_t n, const double *acc0, const double *mag0, const double *acc,
@@ -1090,19 +961,7 @@ int pekf_rotmat_to_quat(int64_t n, const double *M, double *q) {
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(M && q, "null pointer");
-    if (int st = require_device()) return st;
-    if (n == 1) {
-        int32_t st1 = 0;
-        return call1<kCallR2q>({{M, 72}}, {{q, 32}}, &st1);
-    }
-    Staging &s = Staging::get();
-    const size_t b = (size_t)n * sizeof(double);
-    void *in[1], *out[1];
-    if (int st = s.stage_in({{M, 9 * b}}, {4 * b}, in, out)) return st;
-    hipLaunchKernelGGL(k_r2q, PEKF_GRID(n), 0, s.stream(), n, D(const double *, in[0]),
-                       D(double *, out[0]), s.done(grid_for(n, kBlock)));
-    if (int st = launched("k_r2q")) return st;
-    return s.stage_out({{q, 4 * b}}, out);
+    return staged_call<kBlock, call1<kCallR2q>>(k_r2q, "k_r2q", n, {{M, 9}}, {{q, 4}});
 }
 
 }  // extern "C"

@@ -121,18 +121,13 @@ int launch_update(int64_t batch, const double *gyro, const int64_t *t_ns, const 
                   double r, double *x_out, uint32_t flags, hipStream_t stream) {
     const dim3 grid(grid_for(batch, kRunBlock)), block(kRunBlock);
     const bool mixed = flags & PEKF_RUN_MIXED_PRECISION, soa = flags & PEKF_RUN_STATE_SOA;
-#define PEKF_LAUNCH_UPDATE(MX, SO)                                                                \
-    hipLaunchKernelGGL((k_update<MX, SO>), grid, block, 0, stream, batch, gyro, t_ns, acc, mag, missing, \
-                       refs, prev_t, X, P, q, r, x_out)
-    if (mixed) {
-        if (soa) PEKF_LAUNCH_UPDATE(true, true); else PEKF_LAUNCH_UPDATE(true, false);
-    } else {
-        if (soa) PEKF_LAUNCH_UPDATE(false, true); else PEKF_LAUNCH_UPDATE(false, false);
-    }
-#undef PEKF_LAUNCH_UPDATE
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_update");
-    return PEKF_OK;
+    dispatch_bools(
+        [&](auto mx, auto so) {
+            hipLaunchKernelGGL((k_update<mx.value, so.value>), grid, block, 0, stream, batch, gyro, t_ns, acc, mag,
+                               missing, refs, prev_t, X, P, q, r, x_out);
+        },
+        mixed, soa);
+    return launched("k_update");
 }
 
 }  // namespace pekf
@@ -166,27 +161,14 @@ int pekf_run_ext_dev(int64_t batch, int64_t n_steps, int64_t window, int64_t ste
         return launch_run_multi(batch, n_steps, window, step0, gd, am, my, dt_ext, refs, X, P, q, r, traj, counts,
                                 mixed, soa, as_stream(stream));
     // one-record launch (online serving)
-#define PEKF_LAUNCH_ONE(TR, MX, SO, CN, LD)                                                                   \
-    hipLaunchKernelGGL((k_run<TR, MX, SO, CN, true, false, LD>), grid, block, 0, as_stream(stream), batch, n_steps, \
-                       window, step0, gd, am, my, refs, X, P, q, r, traj, counts, dt_ext)
-#define PEKF_LAUNCH_ONE0(TR, MX, SO, CN) \
-    do { if (dt_ext) PEKF_LAUNCH_ONE(TR, MX, SO, CN, true); else PEKF_LAUNCH_ONE(TR, MX, SO, CN, false); } while (0)
-#define PEKF_LAUNCH_ONE1(TR, MX, SO) \
-    do { if (counts) PEKF_LAUNCH_ONE0(TR, MX, SO, true); else PEKF_LAUNCH_ONE0(TR, MX, SO, false); } while (0)
-#define PEKF_LAUNCH_ONE2(TR, MX) \
-    do { if (soa) PEKF_LAUNCH_ONE1(TR, MX, true); else PEKF_LAUNCH_ONE1(TR, MX, false); } while (0)
-    if (traj) {
-        if (mixed) PEKF_LAUNCH_ONE2(true, true); else PEKF_LAUNCH_ONE2(true, false);
-    } else {
-        if (mixed) PEKF_LAUNCH_ONE2(false, true); else PEKF_LAUNCH_ONE2(false, false);
-    }
-#undef PEKF_LAUNCH_ONE2
-#undef PEKF_LAUNCH_ONE1
-#undef PEKF_LAUNCH_ONE0
-#undef PEKF_LAUNCH_ONE
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_run");
-    return PEKF_OK;
+    dispatch_bools(
+        [&](auto tr, auto mx, auto so, auto cn, auto ld) {
+            hipLaunchKernelGGL((k_run<tr.value, mx.value, so.value, cn.value, true, false, ld.value>), grid, block, 0,
+                               as_stream(stream), batch, n_steps, window, step0, gd, am, my, refs, X, P, q, r, traj,
+                               counts, dt_ext);
+        },
+        traj != nullptr, mixed, soa, counts != nullptr, dt_ext != nullptr);
+    return launched("k_run");
 }
 
 int pekf_run_dev(int64_t batch, int64_t n_steps, int64_t window, int64_t step0,
@@ -203,9 +185,7 @@ int pekf_reset_state_dev(int64_t batch, double *X, double *P, void *stream) {
     PEKF_CHECK_ARG(X && P, "null pointer");
     hipLaunchKernelGGL(k_reset, dim3(grid_for(batch, kRunBlock)), dim3(kRunBlock), 0,
                        as_stream(stream), batch, X, P);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_reset");
-    return PEKF_OK;
+    return launched("k_reset");
 }
 
 int pekf_state_layout_dev(int64_t batch, double *X_aos, double *P_aos, double *X_soa, double *P_soa,
@@ -215,9 +195,7 @@ int pekf_state_layout_dev(int64_t batch, double *X_aos, double *P_aos, double *X
     PEKF_CHECK_ARG(X_aos && P_aos && X_soa && P_soa, "null pointer");
     hipLaunchKernelGGL(k_state_layout, dim3(grid_for(batch, kRunBlock)), dim3(kRunBlock), 0,
                        as_stream(stream), batch, X_aos, P_aos, X_soa, P_soa, to_soa);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_state_layout");
-    return PEKF_OK;
+    return launched("k_state_layout");
 }
 
 }  // extern "C"

@@ -202,16 +202,11 @@ extern "C" int pekf_run_rec64_dev(int64_t batch, int64_t n_steps, int64_t window
     const auto *am = static_cast<const double4 *>(plane_am);
     const auto *my = static_cast<const double2 *>(plane_my);
     const hipStream_t s = as_stream(stream);
-#define PEKF_LAUNCH_RUN64(TR, CN)                                                                               \
-    hipLaunchKernelGGL((k_run64<TR, CN>), grid, block, 0, s, batch, n_steps, window, step0, gd, am, my, refs, X, P, \
-                       q, r, traj, counts)
-    if (traj) {
-        if (counts) PEKF_LAUNCH_RUN64(true, true); else PEKF_LAUNCH_RUN64(true, false);
-    } else {
-        if (counts) PEKF_LAUNCH_RUN64(false, true); else PEKF_LAUNCH_RUN64(false, false);
-    }
-#undef PEKF_LAUNCH_RUN64
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_run64");
-    return PEKF_OK;
+    dispatch_bools(
+        [&](auto tr, auto cn) {
+            hipLaunchKernelGGL((k_run64<tr.value, cn.value>), grid, block, 0, s, batch, n_steps, window, step0, gd, am,
+                               my, refs, X, P, q, r, traj, counts);
+        },
+        traj != nullptr, counts != nullptr);
+    return launched("k_run64");
 }

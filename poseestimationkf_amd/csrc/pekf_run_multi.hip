@@ -40,45 +40,25 @@ int launch_run_multi(int64_t batch, int64_t n_steps, int64_t window, int64_t ste
                      double *P, double q, double r, double *traj, const int32_t *counts, bool mixed, bool soa,
                      hipStream_t stream) {
     const dim3 grid(grid_for(batch, kRunBlock)), block(kRunBlock);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, batch, n_steps, window, step0, gd, am, my, refs, X, P, q, r,
+                           traj, counts, dtx);
+    };
+    // the PIN / HOIST variants exist for this one flag combination only: spelled out, soa aside
     if (!traj && !mixed && !counts && !dtx && pin_schedule()) {
-        if (hoist_schedule(batch)) {
-            if (soa)
-                hipLaunchKernelGGL((k_run<false, false, true, false, false, true, false, true>), grid, block, 0, stream,
-                                   batch, n_steps, window, step0, gd, am, my, refs, X, P, q, r, traj, counts, dtx);
-            else
-                hipLaunchKernelGGL((k_run<false, false, false, false, false, true, false, true>), grid, block, 0, stream,
-                                   batch, n_steps, window, step0, gd, am, my, refs, X, P, q, r, traj, counts, dtx);
-        } else if (soa)
-            hipLaunchKernelGGL((k_run<false, false, true, false, false, true>), grid, block, 0, stream, batch, n_steps,
-                               window, step0, gd, am, my, refs, X, P, q, r, traj, counts, dtx);
+        if (hoist_schedule(batch))
+            dispatch_bools(
+                [&](auto so) { launch(k_run<false, false, so.value, false, false, true, false, true>); }, soa);
         else
-            hipLaunchKernelGGL((k_run<false, false, false, false, false, true>), grid, block, 0, stream, batch, n_steps,
-                               window, step0, gd, am, my, refs, X, P, q, r, traj, counts, dtx);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "k_run");
-        return PEKF_OK;
+            dispatch_bools([&](auto so) { launch(k_run<false, false, so.value, false, false, true>); }, soa);
+        return launched("k_run");
     }
-#define PEKF_LAUNCH_RUN(TR, MX, SO, CN, LD)                                                                    \
-    hipLaunchKernelGGL((k_run<TR, MX, SO, CN, false, false, LD>), grid, block, 0, stream, batch, n_steps, window, \
-                       step0, gd, am, my, refs, X, P, q, r, traj, counts, dtx)
-#define PEKF_LAUNCH_RUN0(TR, MX, SO, CN) \
-    do { if (dtx) PEKF_LAUNCH_RUN(TR, MX, SO, CN, true); else PEKF_LAUNCH_RUN(TR, MX, SO, CN, false); } while (0)
-#define PEKF_LAUNCH_RUN1(TR, MX, SO) \
-    do { if (counts) PEKF_LAUNCH_RUN0(TR, MX, SO, true); else PEKF_LAUNCH_RUN0(TR, MX, SO, false); } while (0)
-#define PEKF_LAUNCH_RUN2(TR, MX) \
-    do { if (soa) PEKF_LAUNCH_RUN1(TR, MX, true); else PEKF_LAUNCH_RUN1(TR, MX, false); } while (0)
-    if (traj) {
-        if (mixed) PEKF_LAUNCH_RUN2(true, true); else PEKF_LAUNCH_RUN2(true, false);
-    } else {
-        if (mixed) PEKF_LAUNCH_RUN2(false, true); else PEKF_LAUNCH_RUN2(false, false);
-    }
-#undef PEKF_LAUNCH_RUN2
-#undef PEKF_LAUNCH_RUN1
-#undef PEKF_LAUNCH_RUN0
-#undef PEKF_LAUNCH_RUN
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_run");
-    return PEKF_OK;
+    dispatch_bools(
+        [&](auto tr, auto mx, auto so, auto cn, auto ld) {
+            launch(k_run<tr.value, mx.value, so.value, cn.value, false, false, ld.value>);
+        },
+        traj != nullptr, mixed, soa, counts != nullptr, dtx != nullptr);
+    return launched("k_run");
 }
 
 }  // namespace pekf

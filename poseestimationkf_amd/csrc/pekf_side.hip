@@ -276,12 +276,6 @@ __global__ __launch_bounds__(kSideBlock) void k_rpy(int64_t n, const double *__r
     done.signal();
 }
 
-static int launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what);
-    return PEKF_OK;
-}
-
 }  // namespace pekf
 
 using namespace pekf;
@@ -298,12 +292,12 @@ int pekf_gyro_chain_ext_dev(int64_t batch, int64_t n_steps, int64_t window, int6
     PEKF_CHECK_ARG(n_steps < ((int64_t)1 << 31) && window < ((int64_t)1 << 31), "n_steps and window must be < 2^31");
     const dim3 grid(grid_for(batch, kSideBlock)), block(kSideBlock);
     const float4 *gd = static_cast<const float4 *>(plane_gd);
-    if (dt_ext)
-        hipLaunchKernelGGL(k_gyro_chain<true>, grid, block, 0, as_stream(stream), batch, n_steps, window, step0, gd,
-                           dt_ext, q_gyro, traj);
-    else
-        hipLaunchKernelGGL(k_gyro_chain<false>, grid, block, 0, as_stream(stream), batch, n_steps, window, step0, gd,
-                           nullptr, q_gyro, traj);
+    dispatch_bools(
+        [&](auto longdt) {
+            hipLaunchKernelGGL(k_gyro_chain<longdt.value>, grid, block, 0, as_stream(stream), batch, n_steps, window,
+                               step0, gd, dt_ext, q_gyro, traj);
+        },
+        dt_ext != nullptr);
     return launched("k_gyro_chain");
 }
 
@@ -374,16 +368,7 @@ int pekf_quat_to_rpy(int64_t n, const double *q, double *rpy) {
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(q && rpy, "null pointer");
-    if (int st = require_device()) return st;
-    Staging &s = Staging::get();
-    const size_t b = (size_t)n * sizeof(double);
-    void *in[1], *out[1];
-    if (int st = s.stage_in({{q, 4 * b}}, {3 * b}, in, out)) return st;
-    hipLaunchKernelGGL(k_rpy, dim3(grid_for(n, kSideBlock)), dim3(kSideBlock), 0, s.stream(), n,
-                       static_cast<const double *>(in[0]), static_cast<double *>(out[0]),
-                       s.done(grid_for(n, kSideBlock)));
-    if (int st = launched("k_rpy")) return st;
-    return s.stage_out({{rpy, 3 * b}}, out);
+    return staged_call<kSideBlock>(k_rpy, "k_rpy", n, {{q, 4}}, {{rpy, 3}});  // no n = 1 route
 }
 
 }  // extern "C"

@@ -160,7 +160,5 @@ extern "C" int pekf_synth_dev(int64_t batch, int64_t window, int64_t first_filte
                        scales[1], scales[2], scales[3], scales[4], ar_w,
                        static_cast<float4 *>(plane_gd), static_cast<float4 *>(plane_am),
                        static_cast<float2 *>(plane_my), refs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_synth");
-    return PEKF_OK;
+    return launched("k_synth");
 }

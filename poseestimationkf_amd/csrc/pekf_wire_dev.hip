@@ -675,20 +675,15 @@ extern "C" int pekf_wire_events_ext_dev(int64_t batch, int64_t n_frames, const v
                            static_cast<double4 *>(ev3), first_t2, n2, n3, bad_frame, dev_error, per, part, part_t2,
                            rows ? row_bounds : nullptr);
     };
-    if (rows)
-        launch(k_wire_events<true>);
-    else
-        launch(k_wire_events<false>);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_wire_events");
+    dispatch_bools([&](auto rw) { launch(k_wire_events<rw.value>); }, rows);
+    if (int err = launched("k_wire_events")) return err;
     if (per) {
         hipLaunchKernelGGL(k_wire_rows_finalize, dim3(grid_for(batch, 256)), dim3(256), 0, st, batch, n_frames, chunks,
                            part, part_t2, e2_max, e3_max, static_cast<double4 *>(ev2), static_cast<double4 *>(ev3),
                            first_t2, n2, n3, bad_frame, dev_error);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "k_wire_rows_finalize");
-        e = hipFreeAsync(part, st);
-        if (e != hipSuccess) return hip_fail(e, "k_wire_events chunk counts");
+        if (int err = launched("k_wire_rows_finalize")) return err;
+        hipError_t f = hipFreeAsync(part, st);
+        if (f != hipSuccess) return hip_fail(f, "k_wire_events chunk counts");
     }
     return PEKF_OK;
 }
