@@ -372,7 +372,9 @@ int pekf_magcal_apply_dev(int64_t batch, int64_t n_events, void *ev_planes, cons
  * receives them: "#<phase>,<type>:<x>,<y>,<z>,t:<ns>", spaces to 99 characters, '\n') -> FP64 event planes.
  * frames: [n_frames][batch][100] bytes (device; 4-byte aligned), phone b's frames in order along the first
  * axis (a frame not starting with '#' is no message, e.g. padding; a frame is one message whatever it holds,
- * as the server takes each recv -- a newline inside it does not split it).  Each phase-2 / phase-3 message of phone b
+ * as the server takes each recv -- a newline inside it does not split it; a NUL ends it, as the server's
+ * std::string(buf, 0, n) of a char* does (Server.cpp:97), and a frame left with 30 characters or fewer after
+ * the '#' is no message, Parser.cpp:14).  Each phase-2 / phase-3 message of phone b
  * becomes the next row of ev2 / ev3 ([e2_max][batch] / [e3_max][batch] double4, PEKF_EV_F64_EVENTS' form;
  * type 3 for a Type no sensor takes); rows after its last message get the no-message event.  n2 / n3[batch]:
  * messages per phase (more than e_max: *dev_error |= 2, the extra ones dropped); first_t2[batch]: the time of
@@ -410,7 +412,7 @@ int pekf_wire_events_ext_dev(int64_t batch, int64_t n_frames, const void *frames
  * floats the phone measured.  These two functions give the FP64 event planes those doubles.
  * pekf_wire_parse: the server's parse of such text, one message per line (Parser::run keeps messages
  * starting with '#'; ProcessString skips one of 30 characters or fewer after the '#', newline
- * included).  phase / type: the digits' values; xyz[3n] as strtod (= std::stod) gives them; t_ns as
+ * included; a NUL ends the message, as the server's std::string(buf, 0, n) of a char* does).  phase / type: the digits' values; xyz[3n] as strtod (= std::stod) gives them; t_ns as
  * strtoll (= std::stoll).  All four outputs NULL: count only (*n_events).  A message the server's stod /
  * stoll would throw on returns PEKF_ERR_INVALID naming its line. */
 int pekf_wire_parse(const char *text, int64_t len, int64_t max_events, uint8_t *phase, uint8_t *type, double *xyz,

@@ -1,12 +1,16 @@
 """Restatement of the live server's pre-processing front-end -- TEST INFRASTRUCTURE ONLY.
 
-PARITY PARTLY PINNED: the source is C++ (Kalman Filter Server/PoseEstimator/Parser.cpp,
-KalmanFilter.cpp) that needs Eigen, conio.h and winsock, so it cannot be
-built here and ships no fixtures; this file restates its phase-3 logic by reading the code.
-The low-pass stage (`lpf_step`) is pinned bit for bit by the reference's own Python
-`Test.py:20-35` (the same alpha = 0.1 recurrence from a zero state, run unchanged to produce
-tests/golden/lpf_testpy.npz); the state machine, interpolation and normalisation are
-unpinned.  Used only by tests/test_frontend.py as the checker of pekf_frontend_dev
+PARITY PINNED: the source is C++ (Kalman Filter Server/PoseEstimator/Parser.cpp,
+InitialValues.cpp, KalmanFilter.cpp).  Parser.cpp and InitialValues.cpp are compiled unchanged
+behind stand-in headers (oracle/ref_parser/, built by oracle/Makefile where the reference is
+present) and traced on sessions, time edges, state-machine orders and message forms
+(tests/golden/make_parser_golden.py -> tests/golden/parser.npz); tests/test_parser_golden.py
+holds `records` / `run_frontend` (the state machine, interpolation, normalisation) and
+`initial_values` (phase 2) to that trace bit for bit.  KalmanFilter.cpp needs Eigen, conio.h
+and winsock and is not built: its low-pass stage (`lpf_step`) is pinned bit for
+bit by the reference's own Python `Test.py:20-35` (the same alpha = 0.1 recurrence from a zero
+state, run unchanged to produce tests/golden/lpf_testpy.npz).  Used by the tests of
+pekf_frontend_dev, pekf_frontend_init_dev, pekf_live_dev and the sessions as their checker
 (SURVEY.md §8f-2).
 
 Per filter, events (type '0' acc, '1' gyro, '2' mag; 3 values; integer ns time) go through
@@ -60,22 +64,16 @@ def _normalise(v):
         return [v[0] / d, v[1] / d, v[2] / d]
 
 
-def run_frontend(types, values, times, init_acc, init_mag, t_init, alpha=0.1):
-    """One filter's phase-3 events -> records.
-
-    types (E,) int, values (E,3) float64, times (E,) int64 ns; init_acc / init_mag: phase-2
-    means (raw), t_init: initialisation time.  Returns (gyro (R,3), dt_ns (R,), acc (R,3),
-    mag (R,3)) as float64 -- the values the server logs as gyro / T / Acc_1 / Mag_1.
-    """
+def records(types, values, times, init_acc, init_mag, t_init):
+    """One filter's phase-3 events through Parser::WriteKalmanFilterMeasurement, one item per
+    ExecuteKalmanFilter call: (gyro, time_gyro, acc, mag) -- what the parser hands the filter
+    (SetAngularVelocity, SetAccelerometerMeasurements, SetMagnetometerMeasurements), acc / mag
+    interpolated to the gyro time and normalised, before the filter's low-pass."""
     acc0, t_acc0 = list(map(float, init_acc)), int(t_init)
     mag0, t_mag0 = list(map(float, init_mag)), int(t_init)
     acc1 = mag1 = gyro = None
     t_acc1 = t_mag1 = t_gyro = 0
     gyro_set = acc1_set = mag1_set = False
-    lpf_acc = [0.0, 0.0, 0.0]
-    lpf_mag = [0.0, 0.0, 0.0]
-    prev_t = int(t_init)
-    out_g, out_dt, out_a, out_m = [], [], [], []
     for k in range(len(types)):
         ty, v, t = int(types[k]), [float(x) for x in values[k]], int(times[k])
         if not gyro_set:
@@ -102,15 +100,30 @@ def run_frontend(types, values, times, init_acc, init_mag, t_init, alpha=0.1):
             gyro_set = acc1_set = mag1_set = False
             a = _normalise(_interp(t_acc0, t_acc1, t_gyro, acc0, acc1))
             m = _normalise(_interp(t_mag0, t_mag1, t_gyro, mag0, mag1))
-            lpf_mag = lpf_step(lpf_mag, m, alpha)
-            lpf_acc = lpf_step(lpf_acc, a, alpha)
-            out_g.append(gyro)
-            out_dt.append(t_gyro - prev_t)
-            out_a.append(lpf_acc)
-            out_m.append(lpf_mag)
-            prev_t = t_gyro
+            yield gyro, t_gyro, a, m
             acc0, t_acc0 = acc1, t_acc1
             mag0, t_mag0 = mag1, t_mag1
+
+
+def run_frontend(types, values, times, init_acc, init_mag, t_init, alpha=0.1):
+    """One filter's phase-3 events -> records.
+
+    types (E,) int, values (E,3) float64, times (E,) int64 ns; init_acc / init_mag: phase-2
+    means (raw), t_init: initialisation time.  Returns (gyro (R,3), dt_ns (R,), acc (R,3),
+    mag (R,3)) as float64 -- the values the server logs as gyro / T / Acc_1 / Mag_1.
+    """
+    lpf_acc = [0.0, 0.0, 0.0]
+    lpf_mag = [0.0, 0.0, 0.0]
+    prev_t = int(t_init)
+    out_g, out_dt, out_a, out_m = [], [], [], []
+    for gyro, t_gyro, a, m in records(types, values, times, init_acc, init_mag, t_init):
+        lpf_mag = lpf_step(lpf_mag, m, alpha)
+        lpf_acc = lpf_step(lpf_acc, a, alpha)
+        out_g.append(gyro)
+        out_dt.append(t_gyro - prev_t)
+        out_a.append(lpf_acc)
+        out_m.append(lpf_mag)
+        prev_t = t_gyro
     return (np.asarray(out_g, np.float64).reshape(-1, 3), np.asarray(out_dt, np.int64),
             np.asarray(out_a, np.float64).reshape(-1, 3), np.asarray(out_m, np.float64).reshape(-1, 3))
 
@@ -124,7 +137,7 @@ def initial_values(types, values, times, n_avg=100):
     sum / n, then sum((x - mean)^2) / (n - 1), InitialValues.cpp:20-66) and the sensor counts as
     initialised at its next sample; the first event after all three are initialised builds the
     KalmanFilter at its time, and every later one moves acc_0 / mag_0's time and previousT to its
-    own (:41-62).  PARITY UNPINNED (C++ source that cannot be built here, no fixtures).
+    own (:41-62).  Pinned bit for bit by the reference's compiled parser (tests/test_parser_golden.py).
     Every message counts, whatever its type (a Type char no sensor matches, here 3, adds no sample but
     builds the filter or moves its time once all three are initialised); type NONE (4) is no message
     (stream padding) and is skipped."""

@@ -138,3 +138,18 @@ def run(records, n_steps=None, step0=0, q=1.0, r=0.1, X=None, P=None, want_traj=
     if st:
         raise np.linalg.LinAlgError("Singular matrix")
     return Xs, Ps, traj
+
+
+def run_records64(gyro, dt_ns, acc, mag, acc0, mag0, q=1.0, r=0.1, X=None, P=None):
+    """One filter's float64 records through oracle_run's own loop (ekf_oracle.c: oracle_predict then
+    oracle_correct per record, Q = q I, R = r I, from X = [1, 0, 0, 0], P = I unless given) without the
+    f32 rounding of `run`'s packed 40 B records: gyro / acc / mag (R, 3), dt_ns (R,).  Returns (X, P).
+    `run` on the same records rounded to f32 gives the same chain up to that rounding
+    (tests/test_parser_golden_gpu.py asserts both)."""
+    x = np.array([1.0, 0, 0, 0]) if X is None else np.array(X, np.float64, copy=True)
+    p = np.eye(4) if P is None else np.array(P, np.float64, copy=True)
+    Q, R = np.eye(3) * float(q), np.eye(4) * float(r)
+    for i in range(len(dt_ns)):
+        z, pm, k = predict(gyro[i], dt_ns[i], x, p, Q, R)
+        x, p = correct(mag[i], acc[i], z, pm, k, acc0, mag0)
+    return x, p

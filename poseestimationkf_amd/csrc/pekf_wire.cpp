@@ -9,9 +9,10 @@
 // (KFS/Parser.cpp:12-26, ProcessString) -- the double nearest the printed decimal, which in general is
 // not the float itself (e.g. "0.1" is 0.1, not 0.100000001490116...).
 //
-//  * pekf_wire_parse: the server's own parse of such text (Parser::run's '#' test and ProcessString's
-//    length test and field splitting, strtod / strtoll as std::stod / std::stoll call them, strtod in the
-//    "C" locale, pekf_cnum.hpp).
+//  * pekf_wire_parse: the server's own parse of such text (the message cut at a NUL as Server.cpp:97's
+//    std::string(buf, 0, n) cuts it, Parser::run's '#' test and ProcessString's length test and field
+//    splitting, strtod / strtoll as std::stod / std::stoll call them, strtod in the "C" locale,
+//    pekf_cnum.hpp).
 //  * pekf_f32_wire_values: for samples known only as floats, the double the server would parse from
 //    Float.toString(f).  Float.toString prints the shortest decimal that rounds to f, the closest to f
 //    among those (JDK 19+ specification; for a float whose shortest decimal has one digit it picks the
@@ -195,10 +196,13 @@ int pekf_wire_parse(const char *text, int64_t len, int64_t max_events, uint8_t *
         const char *nl = static_cast<const char *>(std::memchr(text + i, '\n', (size_t)(len - i)));
         const int64_t end = nl ? (nl - text) + 1 : len;
         ++line;
+        // The server's message is std::string(buf, 0, n) of a char *buf (Server.cpp:97): through strlen, so
+        // it ends at the frame's first NUL, whatever follows.
+        const int64_t mend = i + (int64_t)strnlen(text + i, (size_t)(end - i));
         // Parser::run: only messages starting with '#', without it; ProcessString: longer than 30
-        if (text[i] == '#' && end - i - 1 > 30) {
+        if (text[i] == '#' && mend - i - 1 > 30) {
             Message m;
-            if (!parse_fast(text + i + 1, text + end, m) && !parse_general(msg, text + i + 1, end - i - 1, m))
+            if (!parse_fast(text + i + 1, text + mend, m) && !parse_general(msg, text + i + 1, mend - i - 1, m))
                 return pekf::set_error(PEKF_ERR_INVALID, "wire message %lld: not '#<phase>,<type>:<x>,<y>,<z>,t:<ns>'",
                                        (long long)line);  // the server's std::stod / std::stoll would throw here
             if (fill) {

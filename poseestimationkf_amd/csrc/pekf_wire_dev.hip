@@ -4,8 +4,9 @@
 //
 // Each message the Android client sends is one 100-byte frame: "#<phase>,<type>:<x>,<y>,<z>,t:<ns>" padded
 // with spaces to 99 characters plus println's newline (ASC/MessageSender.java:217-233); the server reads
-// exactly such frames (recv of messageSize = 100, KFS/Server.cpp:35,84), keeps those that start with '#'
-// (Parser::run, KFS/Parser.cpp:357-363) and parses them in ProcessString (:12-26): phase = the first
+// exactly such frames (recv of messageSize = 100, KFS/Server.cpp:35,84; the message ends at a frame's first
+// NUL, :97), keeps those that start with '#' (Parser::run, KFS/Parser.cpp:357-363) and parses those of more
+// than 30 characters after it in ProcessString (:12-26): phase = the first
 // character, Type = the first character before the first ':', each value std::stod of the text before the
 // next ',', the time std::stoll of the text after "t:".  One lane per phone walks its frames in order
 // ([n_frames][batch][100] bytes: a wave's 64 frames of one index are 6,400 contiguous bytes, brought
@@ -309,8 +310,8 @@ __device__ __forceinline__ bool wire_number_fast(const uint32_t *fr32, const dou
     return ok;
 }
 
-// "t:" and 1..16 digits at byte i, then any non-digit
-__device__ __forceinline__ bool wire_time_fast(const uint32_t *fr32, int i, long long &t) {
+// "t:" and 1..16 digits at byte i, then any non-digit; end: the byte after the digits
+__device__ __forceinline__ bool wire_time_fast(const uint32_t *fr32, int i, long long &t, int &end) {
     const int a = i >> 2, s = i & 3;
     const uint32_t d0 = fr32[a], d1 = fr32[a + 1], d2 = fr32[a + 2], d3 = fr32[a + 3], d4 = fr32[a + 4],
                    d5 = fr32[a + 5];
@@ -329,6 +330,7 @@ __device__ __forceinline__ bool wire_time_fast(const uint32_t *fr32, int i, long
     wire_rd64(fr32, i + 2, lo, hi);
     const uint32_t A = LA > 0 ? digits_value(lo, hi, LA < 8 ? LA : 8) : 0u;
     t = (long long)((uint64_t)A * 100000000ull + B);
+    end = i + 2 + n;
     return ok;
 }
 
@@ -338,26 +340,41 @@ __device__ __forceinline__ int wire_frame_fast(const uint32_t *fr32, const doubl
     if ((h0 & 0xffu) != '#') return 1;
     m.phase = (uint8_t)(h0 >> 8);
     m.type = (uint8_t)(h0 >> 24);
-    bool ok = (h1 & 0xffu) == ':' && m.type != ':' && m.type != 0;  // one Type character, the first ':'
+    // one Type character, the first ':'; byte 2, which the server drops unread (str.substr(2)), is no NUL
+    bool ok = (h1 & 0xffu) == ':' && m.type != ':' && m.type != 0 && ((h0 >> 16) & 0xffu) != 0;
     int i = 5;
     ok = wire_number_fast(fr32, p10, i, m.v[0]) && ok;
     ok = wire_number_fast(fr32, p10, i, m.v[1]) && ok;
     ok = wire_number_fast(fr32, p10, i, m.v[2]) && ok;
-    ok = wire_time_fast(fr32, i, m.t) && ok;
-    return ok ? 0 : 3;
+    int end;
+    ok = wire_time_fast(fr32, i, m.t, end) && ok;
+    // Where ok, no byte from 2 up to the time's last digit is a NUL: byte 2 is tested above, the Type is
+    // no NUL, and every other byte is a character of the form.  (A NUL phase, byte 1, is a message of no
+    // phase: skipped by the caller, as the server skips its message of one character.)  A NUL after the
+    // time ends the server's message there (see wire_frame), and a message of 30 characters or fewer after
+    // '#' is skipped: a time that ends within the first 31 bytes leaves that to wire_frame (no client's
+    // does: "#p,T:" and three numbers take 17 bytes at least, "t:" and a sensor clock's digits 15).
+    return ok && end > 31 ? 0 : 3;
 }
 
-// 0: a message (m filled); 1: no message (no '#': Parser::run skips it); 2: not parsed here (see above)
+// 0: a message (m filled); 1: no message (no '#': Parser::run skips it; or cut short by a NUL: ProcessString
+// does); 2: not parsed here (see above)
 __device__ int wire_frame(const uint8_t *fr, WireMsg &m) {
     auto ch = [&](int j) -> unsigned {
         const unsigned c = fr[j < kWireFrame ? j : kWireFrame - 1];
         return j < kWireFrame ? c : 0u;
     };
     if (fr[0] != '#') return 1;
+    // The server's message is std::string(buf, 0, n) of a char *buf (Server.cpp:97): through strlen, so it
+    // ends at the frame's first NUL; ProcessString takes it if more than 30 characters follow the '#'
+    // (Parser.cpp:14).  What is parsed below stops at that NUL too: no token reads past one.
+    int len = kWireFrame;
+    for (int j = kWireFrame - 1; j > 0; --j) len = fr[j] == 0 ? j : len;
+    if (len - 1 <= 30) return 1;
     m.phase = fr[1];
     int i = 3;  // str.substr(2) of the text after '#'
     bool cact = true, nul = false;
-    for (;;) {  // to the first ':' (a NUL before it: strchr's end, not the server's message)
+    for (;;) {  // to the first ':' (a NUL before it: the message has none, and std::stod("") throws)
         const unsigned c = ch(i);
         nul |= cact && c == 0 && i < kWireFrame;
         cact = cact && i < kWireFrame && c != ':' && c != 0;

@@ -598,9 +598,16 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     and whose frames a small batch splits over several waves; phase 2 and phase 3 read only the rows that
     hold messages (65,536 phones: 5.0 ms against 6.0 compacted with aligned rows, 5.0 against 8.0 ms with
     rows 64 apart).  calibration: as run_session (the phones' phase-1 frames are skipped by the device
-    parse: calibrate from wire.events_from_wire(texts, ..., phase=1))."""
-    w = wire_events(frames, stream, frame_rows)
+    parse: calibrate from wire.events_from_wire(texts, ..., phase=1)).  Raises ValueError, before anything
+    is launched, if filters.batch is not the frames' phone count."""
     K = filters.batch
+    if isinstance(frames, tuple):
+        Kf = int(frames[2])
+    else:
+        Kf = np.shape(frames)[1] if np.ndim(frames) == 3 else K  # (wire_events refuses any other shape)
+    if Kf != K:  # the planes' column stride is the frames' phone count: any other batch reads them wrong
+        raise ValueError("the frames are of %d phones, the filters of %d" % (Kf, K))
+    w = wire_events(frames, stream, frame_rows)
     ib, tib, rb = DeviceBuffer(48 * K), DeviceBuffer(8 * K), DeviceBuffer(4 * K)
     if calibration is not None:  # with frame rows the no-message rows are walked too (and left as they are)
         _apply_calibration(calibration, K, w["E2"], w["ev2"].ptr, EV_F64_EVENTS, stream)

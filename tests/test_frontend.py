@@ -1,12 +1,12 @@
 """Server front-end: raw phone events -> records -> filter, and the phase-2
 initial means / variances that phase 3 starts from (KFS/Parser.cpp:36-58,84-140, InitialValues.cpp).
 
-PARTLY PINNED: the checker is oracle/frontend_numpy.py, a restatement of the C++ front-end
-(KFS/Parser.cpp, KFS/KalmanFilter.cpp), which cannot be built here (Eigen, Windows headers) and
-ships no fixtures.  Its low-pass stage is pinned by the reference's own Test.py
-(tests/golden/lpf_testpy.npz, made by tests/golden/make_lpf_golden.py); the state machine,
-interpolation and normalisation are not.  The filter that consumes the records is pinned as
-everywhere else."""
+PINNED: the checker is oracle/frontend_numpy.py, a restatement of the C++ front-end
+(KFS/Parser.cpp, KFS/InitialValues.cpp, KFS/KalmanFilter.cpp).  Its state machine, interpolation,
+normalisation and phase 2 are held bit for bit to the reference's own compiled Parser.cpp
+(tests/golden/parser.npz, tests/test_parser_golden.py); its low-pass stage is pinned by the
+reference's own Test.py (tests/golden/lpf_testpy.npz, made by tests/golden/make_lpf_golden.py).
+The filter that consumes the records is pinned as everywhere else."""
 import numpy as np
 import pytest
 

@@ -8,7 +8,7 @@ Two record precisions (pekf_live_ext_dev's PEKF_EV_F32_RECORDS):
 * FP64 records (the default, what the server's filter receives: KFS/KalmanFilter.cpp:279-303) against
   the unrounded oracle chain (oracle/frontend_numpy.py float64 records -> oracle/ekf_numpy.py, the
   reference's own arithmetic), where the f32 records' rounding shows as ~1e-8 (measured, asserted).
-The oracle's front-end half is partly pinned (see tests/test_frontend.py)."""
+The oracle's front-end half is pinned by the reference's compiled parser (see tests/test_frontend.py)."""
 import numpy as np
 import pytest
 
