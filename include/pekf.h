@@ -383,7 +383,8 @@ int pekf_magcal_apply_dev(int64_t batch, int64_t n_events, void *ev_planes, cons
  * of at most 19 significant digits within 1e-80 .. 1e80 of the exponent; an exact big-integer path where
  * one IEEE operation is not exact), "NaN", "Infinity", "-Infinity"; a phone's first frame in another form,
  * or with a time of 2^51 ns or more, stops that phone: bad_frame[b] (may be NULL) = its index (-1: none),
- * *dev_error |= 1 (parse such a stream with pekf_wire_parse).  Phase-1 and other phases are skipped. */
+ * *dev_error |= 1 (parse such a stream with pekf_wire_parse).  Messages of any other phase are skipped here;
+ * pekf_wire_events_p1_dev keeps the phase-1 messages too (the calibration's, pekf_magcal_dev). */
 int pekf_wire_events_dev(int64_t batch, int64_t n_frames, const void *frames, int64_t e2_max, int64_t e3_max,
                          void *ev2, void *ev3, int64_t *first_t2, int32_t *n2, int32_t *n3, int32_t *bad_frame,
                          int *dev_error, void *stream);
@@ -404,6 +405,23 @@ int pekf_wire_events_dev(int64_t batch, int64_t n_frames, const void *frames, in
 int pekf_wire_events_ext_dev(int64_t batch, int64_t n_frames, const void *frames, int64_t e2_max, int64_t e3_max,
                              void *ev2, void *ev3, int64_t *first_t2, int32_t *n2, int32_t *n3, int32_t *bad_frame,
                              int *dev_error, int32_t *row_bounds, uint32_t flags, void *stream);
+/* pekf_wire_events_ext_dev with a third plane, the phase-1 messages: phase 1 (pekf_magcal_dev) from wire
+ * frames with no host parse.  Every message whose phase character is '1' becomes the next row of ev1
+ * ([e1_max][batch] double4, PEKF_EV_F64_EVENTS' form; n1[batch] counts them, more than e1_max: *dev_error
+ * |= 2), whatever its Type: the server hands every phase-1 sample to the calibration
+ * (KFS/Parser.cpp:30-34,144-147), and pekf_magcal_dev takes every message as a sample.  The type bits are
+ * those of the other planes ('0'..'2', else 3) and x, y, z the same std::stod values.  The server never reads
+ * a phase-1 message's time, but std::stoll must accept it: a time in a form it refuses stops the phone as
+ * above, while one of 2^51 ns or more, which the event cannot hold, is stored as 0 -- the message stays a
+ * message and counts in n1 (phases 2 and 3 keep their 2^51 refusal).  PEKF_WIRE_FRAME_ROWS: row f of ev1 is
+ * frame f's message or the no-message event (needs e1_max >= n_frames too; 32 B more written per frame; the
+ * chunks' stream-ordered allocation is the same 24 B).  row_bounds: 3 int32, [2] = 1 + the last row holding a
+ * phase-1 message of any phone (pekf_magcal_dev needs ev1's first [2] rows).  ev2, ev3, n2, n3, first_t2,
+ * bad_frame and row_bounds[0..1] are pekf_wire_events_ext_dev's, bit for bit. */
+int pekf_wire_events_p1_dev(int64_t batch, int64_t n_frames, const void *frames, int64_t e1_max, int64_t e2_max,
+                            int64_t e3_max, void *ev1, void *ev2, void *ev3, int64_t *first_t2, int32_t *n1,
+                            int32_t *n2, int32_t *n3, int32_t *bad_frame, int *dev_error, int32_t *row_bounds,
+                            uint32_t flags, void *stream);
 
 /* ---------------- the phone -> server wire: host code ----------------
  * The Android client sends each sample as text, Float.toString of each value

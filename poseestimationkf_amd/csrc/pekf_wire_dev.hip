@@ -17,6 +17,8 @@
 // event to row f of the other plane): every lane of a wave stores one row however far the phones' message
 // counts drift apart, and since no row depends on the frames before it, a small batch's frames are split
 // into chunks over several waves, their counts combined by k_wire_rows_finalize.
+// pekf_wire_events_p1_dev's kernels (P1) keep the phase-1 messages as well, in a third plane: pekf_magcal_dev's
+// input, the calibration without a host parse.
 //
 // Frames in the client's own form are parsed without a character loop (wire_frame_fast: digit masks of
 // 16-byte windows, 8 digits per SWAR conversion); any other frame by wire_frame, the general parser.
@@ -424,12 +426,19 @@ __device__ int wire_frame(const uint8_t *fr, WireMsg &m) {
 // every lane, and the registers spill).
 // ROWS (PEKF_WIRE_FRAME_ROWS): frame f's message goes to row f of its phase's plane and the no-message
 // event to row f of the other, so every lane of a wave stores the same row (see pekf.h).
-template <bool ROWS>
+// P1 (pekf_wire_events_p1_dev): a third plane, ev1 / n1, of the phase-1 messages -- every one whatever its
+// Type, as the server hands each to the calibration (KFS/Parser.cpp:30-34,144-147); bounds gets a third
+// word, 1 + the last row holding one.  One event is built and its plane selected, the other planes get the
+// no-message constant: one more pointer and counter in the fast loop, no second or third row value.
+// The P1 = false kernels take the same arguments and read none of the last three: their code is the
+// kernels' of before the third plane, instruction for instruction.
+template <bool ROWS, bool P1>
 __global__ __launch_bounds__(kWireBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_wire_events(
     int64_t batch, int64_t n_frames, const uint32_t *__restrict__ frames, int64_t e2_max, int64_t e3_max,
     double4 *__restrict__ ev2, double4 *__restrict__ ev3, int64_t *__restrict__ first_t2, int32_t *__restrict__ n2,
     int32_t *__restrict__ n3, int32_t *__restrict__ bad_frame, int *__restrict__ err, int64_t f_per_chunk,
-    int4 *__restrict__ part, int64_t *__restrict__ part_t2, int32_t *__restrict__ bounds) {
+    int4 *__restrict__ part, int64_t *__restrict__ part_t2, int32_t *__restrict__ bounds, int64_t e1_max,
+    double4 *__restrict__ ev1, int32_t *__restrict__ n1) {
     // (ROWS, f_per_chunk > 0: block row blockIdx.y parses frames [fb, fe) and leaves its counts, first
     // phase-2 time and refused frame in part / part_t2 [chunk][batch] for k_wire_rows_finalize)
     const int64_t fb = f_per_chunk > 0 ? (int64_t)blockIdx.y * f_per_chunk : 0;
@@ -486,45 +495,92 @@ __global__ __launch_bounds__(kWireBlock) __attribute__((amdgpu_waves_per_eu(4)))
     int32_t c2 = 0, c3 = 0, bad = -1, resume = -1;
     int32_t end2 = 0, from3 = 0;  // (ROWS, bounds) 1 + the last phase-2 row, n_frames - the first phase-3 row
     int64_t t2 = 0;
+    [[maybe_unused]] int32_t c1 = 0, end1 = 0;  // (P1) phase-1 messages; (ROWS, bounds) 1 + the last phase-1 row
     const double4 none = ev64_null();
     // One parsed frame: a message to its phase's next row (ROWS: to row f, and the no-message event to
     // row f of the other plane); a refused frame ends the phone
+    // P1: one event is built and the plane it goes to selected (ph: 1..3; 0: no message of these phases, and
+    // the event is the no-message one).  The server never reads a phase-1 message's time (stoll has accepted
+    // it by here): one the event cannot hold is stored as 0, and the message stays a message.
     auto take = [&](int st, const WireMsg &m, int64_t f) {
-        double4 e2r = none, e3r = none;  // (ROWS) row f of each plane
-        if (st == 2) {
-            bad = (int32_t)f;
-        } else if (st == 0 && (m.phase == '2' || m.phase == '3')) {  // phase 1 (calibration), others: skipped
-            const double td = (double)m.t;
-            if (!(fabs(td) < 2251799813685248.0)) {  // the FP64 event's time limit, 2^51 ns
+        if constexpr (P1) {
+            // (the selects below are of values, copies of what the lambda captures: a select between the
+            // captures themselves is one of their addresses, and keeps the closure in scratch)
+            double4 *const p1 = ev1, *const p2 = ev2, *const p3 = ev3;
+            int ph = 0;
+            double4 e = none;
+            if (st == 2) {
                 bad = (int32_t)f;
-            } else {
-                const uint32_t ty = (m.type >= '0' && m.type <= '2') ? (uint32_t)(m.type - '0') : 3u;
-                const double4 e = make_double4(m.v[0], m.v[1], m.v[2],
-                                               __longlong_as_double(__double_as_longlong(td) | (long long)ty));
-                if (m.phase == '2') {
-                    if (c2 == 0) t2 = m.t;
-                    if constexpr (ROWS) {
-                        e2r = e;
-                        end2 = (int32_t)f + 1;
-                    }
-                    else if (c2 < e2_max)
-                        ev2[(int64_t)c2 * batch + b] = e;
-                    ++c2;
+            } else if (st == 0 && m.phase >= '1' && m.phase <= '3') {
+                double td = (double)m.t;
+                const bool fits = fabs(td) < 2251799813685248.0;  // the FP64 event's time limit, 2^51 ns
+                if (m.phase == '1' && !fits) td = 0.0;
+                if (m.phase != '1' && !fits) {
+                    bad = (int32_t)f;
                 } else {
-                    if constexpr (ROWS) {
-                        e3r = e;
-                        if (from3 == 0) from3 = (int32_t)(n_frames - f);
-                    }
-                    else if (c3 < e3_max)
-                        ev3[(int64_t)c3 * batch + b] = e;
-                    ++c3;
+                    const uint32_t ty = (m.type >= '0' && m.type <= '2') ? (uint32_t)(m.type - '0') : 3u;
+                    e = make_double4(m.v[0], m.v[1], m.v[2],
+                                     __longlong_as_double(__double_as_longlong(td) | (long long)ty));
+                    ph = m.phase - '0';
+                    if (ph == 2 && c2 == 0) t2 = m.t;
                 }
             }
-        }
-        if constexpr (ROWS) {
-            if (bad < 0) {  // (a stopped phone's rows are filled at the end)
-                ev2[f * batch + b] = e2r;
-                ev3[f * batch + b] = e3r;
+            if constexpr (ROWS) {
+                if (bad < 0) {  // (a stopped phone's rows are filled at the end)
+                    double4 *dst = ph == 1 ? p1 : (ph == 2 ? p2 : p3);  // (ph 0: the no-message event to all three)
+                    double4 *oa = ph == 1 ? p2 : p1, *ob = ph == 1 || ph == 2 ? p3 : p2;
+                    dst[f * batch + b] = e;
+                    oa[f * batch + b] = none;
+                    ob[f * batch + b] = none;
+                }
+                if (ph == 1) end1 = (int32_t)f + 1;
+                if (ph == 2) end2 = (int32_t)f + 1;
+                if (ph == 3 && from3 == 0) from3 = (int32_t)(n_frames - f);
+            } else if (ph) {
+                double4 *dst = ph == 1 ? p1 : (ph == 2 ? p2 : p3);
+                const int32_t n1c = c1, n2c = c2, n3c = c3;
+                const int64_t m1 = e1_max, m2 = e2_max, m3 = e3_max;
+                const int32_t c = ph == 1 ? n1c : (ph == 2 ? n2c : n3c);
+                if (c < (ph == 1 ? m1 : (ph == 2 ? m2 : m3))) dst[(int64_t)c * batch + b] = e;
+            }
+            c1 += ph == 1, c2 += ph == 2, c3 += ph == 3;
+        } else {
+            double4 e2r = none, e3r = none;  // (ROWS) row f of each plane
+            if (st == 2) {
+                bad = (int32_t)f;
+            } else if (st == 0 && (m.phase == '2' || m.phase == '3')) {  // phase 1 (calibration), others: skipped
+                const double td = (double)m.t;
+                if (!(fabs(td) < 2251799813685248.0)) {  // the FP64 event's time limit, 2^51 ns
+                    bad = (int32_t)f;
+                } else {
+                    const uint32_t ty = (m.type >= '0' && m.type <= '2') ? (uint32_t)(m.type - '0') : 3u;
+                    const double4 e = make_double4(m.v[0], m.v[1], m.v[2],
+                                                   __longlong_as_double(__double_as_longlong(td) | (long long)ty));
+                    if (m.phase == '2') {
+                        if (c2 == 0) t2 = m.t;
+                        if constexpr (ROWS) {
+                            e2r = e;
+                            end2 = (int32_t)f + 1;
+                        }
+                        else if (c2 < e2_max)
+                            ev2[(int64_t)c2 * batch + b] = e;
+                        ++c2;
+                    } else {
+                        if constexpr (ROWS) {
+                            e3r = e;
+                            if (from3 == 0) from3 = (int32_t)(n_frames - f);
+                        }
+                        else if (c3 < e3_max)
+                            ev3[(int64_t)c3 * batch + b] = e;
+                        ++c3;
+                    }
+                }
+            }
+            if constexpr (ROWS) {
+                if (bad < 0) {  // (a stopped phone's rows are filled at the end)
+                    ev2[f * batch + b] = e2r;
+                    ev3[f * batch + b] = e3r;
+                }
             }
         }
     };
@@ -569,15 +625,17 @@ __global__ __launch_bounds__(kWireBlock) __attribute__((amdgpu_waves_per_eu(4)))
         for (int d = 1; d < kWireBlock; d <<= 1) {
             end2 = max(end2, __shfl_xor(end2, d));
             from3 = max(from3, __shfl_xor(from3, d));
+            if constexpr (P1) end1 = max(end1, __shfl_xor(end1, d));
         }
         if (lane == 0) {
             atomicMax(bounds, end2);
             atomicMax(bounds + 1, from3);
+            if constexpr (P1) atomicMax(bounds + 2, end1);
         }
     }
     if (b >= batch) return;
     if (part) {
-        part[(int64_t)blockIdx.y * batch + b] = make_int4(c2, c3, bad, 0);
+        part[(int64_t)blockIdx.y * batch + b] = make_int4(c2, c3, bad, P1 ? c1 : 0);
         part_t2[(int64_t)blockIdx.y * batch + b] = t2;
         return;
     }
@@ -585,15 +643,20 @@ __global__ __launch_bounds__(kWireBlock) __attribute__((amdgpu_waves_per_eu(4)))
         const int64_t r0 = bad >= 0 ? bad : n_frames;
         for (int64_t e = r0; e < e2_max; ++e) ev2[e * batch + b] = none;
         for (int64_t e = r0; e < e3_max; ++e) ev3[e * batch + b] = none;
+        if constexpr (P1)
+            for (int64_t e = r0; e < e1_max; ++e) ev1[e * batch + b] = none;
     } else {
         for (int64_t e = c2; e < e2_max; ++e) ev2[e * batch + b] = none;
         for (int64_t e = c3; e < e3_max; ++e) ev3[e * batch + b] = none;
+        if constexpr (P1)
+            for (int64_t e = c1; e < e1_max; ++e) ev1[e * batch + b] = none;
     }
     n2[b] = c2;
     n3[b] = c3;
+    if constexpr (P1) n1[b] = c1;
     first_t2[b] = t2;
     if (bad_frame) bad_frame[b] = bad;
-    const int flags = (bad >= 0 ? 1 : 0) | (c2 > e2_max || c3 > e3_max ? 2 : 0);
+    const int flags = (bad >= 0 ? 1 : 0) | (c2 > e2_max || c3 > e3_max || (P1 && c1 > e1_max) ? 2 : 0);
     if (flags && err) atomicOr(err, flags);
 }
 
@@ -605,16 +668,20 @@ __global__ __launch_bounds__(256) void k_wire_rows_finalize(int64_t batch, int64
                                                             int64_t e3_max, double4 *__restrict__ ev2,
                                                             double4 *__restrict__ ev3, int64_t *__restrict__ first_t2,
                                                             int32_t *__restrict__ n2, int32_t *__restrict__ n3,
-                                                            int32_t *__restrict__ bad_frame, int *__restrict__ err) {
+                                                            int32_t *__restrict__ bad_frame, int *__restrict__ err,
+                                                            int64_t e1_max, double4 *__restrict__ ev1,
+                                                            int32_t *__restrict__ n1) {
+    // (ev1 / n1: the phase-1 plane and counts, the chunks' fourth partial count; null without them)
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
-    int32_t c2 = 0, c3 = 0, bad = -1;
+    int32_t c1 = 0, c2 = 0, c3 = 0, bad = -1;
     int64_t t2 = 0;
     for (int64_t ch = 0; ch < n_chunks; ++ch) {
         const int4 p = part[ch * batch + b];
         if (c2 == 0 && p.x > 0) t2 = part_t2[ch * batch + b];
         c2 += p.x;
         c3 += p.y;
+        c1 += p.w;
         if (p.z >= 0) {  // the phone stopped here: later chunks' frames are not its messages
             bad = p.z;
             break;
@@ -624,6 +691,10 @@ __global__ __launch_bounds__(256) void k_wire_rows_finalize(int64_t batch, int64
     const int64_t r0 = bad >= 0 ? bad : n_frames;
     for (int64_t e = r0; e < e2_max; ++e) ev2[e * batch + b] = none;
     for (int64_t e = r0; e < e3_max; ++e) ev3[e * batch + b] = none;
+    if (n1) {
+        for (int64_t e = r0; e < e1_max; ++e) ev1[e * batch + b] = none;
+        n1[b] = c1;
+    }
     n2[b] = c2;
     n3[b] = c3;
     first_t2[b] = t2;
@@ -635,21 +706,26 @@ __global__ __launch_bounds__(256) void k_wire_rows_finalize(int64_t batch, int64
 
 using namespace pekf;
 
-extern "C" int pekf_wire_events_ext_dev(int64_t batch, int64_t n_frames, const void *frames, int64_t e2_max,
-                                        int64_t e3_max, void *ev2, void *ev3, int64_t *first_t2, int32_t *n2,
-                                        int32_t *n3, int32_t *bad_frame, int *dev_error, int32_t *row_bounds,
-                                        uint32_t flags, void *stream) {
-    PEKF_CHECK_ARG(batch >= 0 && n_frames >= 0 && e2_max >= 0 && e3_max >= 0, "negative size");
+// The two entries' checks and launches.  p1: the phase-1 plane too (ev1, e1_max, n1; a 3-word row_bounds);
+// without it those three are 0 / null and pass every check.
+static int wire_events(bool p1, int64_t batch, int64_t n_frames, const void *frames, int64_t e1_max, int64_t e2_max,
+                       int64_t e3_max, void *ev1, void *ev2, void *ev3, int64_t *first_t2, int32_t *n1, int32_t *n2,
+                       int32_t *n3, int32_t *bad_frame, int *dev_error, int32_t *row_bounds, uint32_t flags,
+                       void *stream) {
+    PEKF_CHECK_ARG(batch >= 0 && n_frames >= 0 && e1_max >= 0 && e2_max >= 0 && e3_max >= 0, "negative size");
     PEKF_CHECK_ARG((flags & ~(uint32_t)PEKF_WIRE_FRAME_ROWS) == 0, "unknown flags");
     const bool rows = flags & PEKF_WIRE_FRAME_ROWS;
-    PEKF_CHECK_ARG(!rows || (e2_max >= n_frames && e3_max >= n_frames),
+    PEKF_CHECK_ARG(!rows || ((!p1 || e1_max >= n_frames) && e2_max >= n_frames && e3_max >= n_frames),
                    "PEKF_WIRE_FRAME_ROWS: the planes need a row per frame index (e_max >= n_frames)");
     if (batch == 0) return PEKF_OK;
     PEKF_CHECK_ARG(frames || n_frames == 0, "null pointer");
     PEKF_CHECK_ARG((ev2 || e2_max == 0) && (ev3 || e3_max == 0) && first_t2 && n2 && n3, "null pointer");
-    PEKF_CHECK_ARG((uintptr_t)frames % 4 == 0 && (uintptr_t)ev2 % 16 == 0 && (uintptr_t)ev3 % 16 == 0,
+    PEKF_CHECK_ARG(!p1 || ((ev1 || e1_max == 0) && n1), "null pointer");
+    PEKF_CHECK_ARG((uintptr_t)frames % 4 == 0 && (uintptr_t)ev1 % 16 == 0 && (uintptr_t)ev2 % 16 == 0 &&
+                       (uintptr_t)ev3 % 16 == 0,
                    "misaligned buffers");
-    PEKF_CHECK_ARG(n_frames < ((int64_t)1 << 31) && e2_max < ((int64_t)1 << 31) && e3_max < ((int64_t)1 << 31),
+    PEKF_CHECK_ARG(n_frames < ((int64_t)1 << 31) && e1_max < ((int64_t)1 << 31) && e2_max < ((int64_t)1 << 31) &&
+                       e3_max < ((int64_t)1 << 31),
                    "n_frames and e_max must be < 2^31");
     // Frame rows need no count before a frame's store: where the grid leaves SIMDs short of 4 waves, the
     // frames are split into chunks parsed by separate waves (PEKF_WIRE_CHUNKS=n forces n) and their
@@ -678,7 +754,7 @@ extern "C" int pekf_wire_events_ext_dev(int64_t batch, int64_t n_frames, const v
     int64_t *part_t2 = nullptr;
     hipStream_t st = as_stream(stream);
     if (rows && row_bounds) {
-        hipError_t z = hipMemsetAsync(row_bounds, 0, 2 * sizeof(int32_t), st);
+        hipError_t z = hipMemsetAsync(row_bounds, 0, (p1 ? 3 : 2) * sizeof(int32_t), st);
         if (z != hipSuccess) return hip_fail(z, "k_wire_events row bounds");
     }
     if (per) {
@@ -690,19 +766,35 @@ extern "C" int pekf_wire_events_ext_dev(int64_t batch, int64_t n_frames, const v
         hipLaunchKernelGGL(kernel, dim3(waves, per ? chunks : 1), dim3(kWireBlock), 0, st, batch, n_frames,
                            static_cast<const uint32_t *>(frames), e2_max, e3_max, static_cast<double4 *>(ev2),
                            static_cast<double4 *>(ev3), first_t2, n2, n3, bad_frame, dev_error, per, part, part_t2,
-                           rows ? row_bounds : nullptr);
+                           rows ? row_bounds : nullptr, e1_max, static_cast<double4 *>(ev1), n1);
     };
-    dispatch_bools([&](auto rw) { launch(k_wire_events<rw.value>); }, rows);
+    dispatch_bools([&](auto rw, auto ph1) { launch(k_wire_events<rw.value, ph1.value>); }, rows, p1);
     if (int err = launched("k_wire_events")) return err;
     if (per) {
         hipLaunchKernelGGL(k_wire_rows_finalize, dim3(grid_for(batch, 256)), dim3(256), 0, st, batch, n_frames, chunks,
                            part, part_t2, e2_max, e3_max, static_cast<double4 *>(ev2), static_cast<double4 *>(ev3),
-                           first_t2, n2, n3, bad_frame, dev_error);
+                           first_t2, n2, n3, bad_frame, dev_error, e1_max, static_cast<double4 *>(ev1), n1);
         if (int err = launched("k_wire_rows_finalize")) return err;
         hipError_t f = hipFreeAsync(part, st);
         if (f != hipSuccess) return hip_fail(f, "k_wire_events chunk counts");
     }
     return PEKF_OK;
+}
+
+extern "C" int pekf_wire_events_ext_dev(int64_t batch, int64_t n_frames, const void *frames, int64_t e2_max,
+                                        int64_t e3_max, void *ev2, void *ev3, int64_t *first_t2, int32_t *n2,
+                                        int32_t *n3, int32_t *bad_frame, int *dev_error, int32_t *row_bounds,
+                                        uint32_t flags, void *stream) {
+    return wire_events(false, batch, n_frames, frames, 0, e2_max, e3_max, nullptr, ev2, ev3, first_t2, nullptr, n2, n3,
+                       bad_frame, dev_error, row_bounds, flags, stream);
+}
+
+extern "C" int pekf_wire_events_p1_dev(int64_t batch, int64_t n_frames, const void *frames, int64_t e1_max,
+                                       int64_t e2_max, int64_t e3_max, void *ev1, void *ev2, void *ev3,
+                                       int64_t *first_t2, int32_t *n1, int32_t *n2, int32_t *n3, int32_t *bad_frame,
+                                       int *dev_error, int32_t *row_bounds, uint32_t flags, void *stream) {
+    return wire_events(true, batch, n_frames, frames, e1_max, e2_max, e3_max, ev1, ev2, ev3, first_t2, n1, n2, n3,
+                       bad_frame, dev_error, row_bounds, flags, stream);
 }
 
 extern "C" int pekf_wire_events_dev(int64_t batch, int64_t n_frames, const void *frames, int64_t e2_max,

@@ -481,19 +481,33 @@ def calibrate_magnetometer(ev, n_cal=100, events="f32"):
     if "t_init" not in ev:
         ev = dict(ev, t_init=np.zeros(K, np.int64))
     evb, E, flags = _event_planes(ev, events)
-    cal, fit, st = DeviceBuffer(96 * K), DeviceBuffer(48 * K), DeviceBuffer(4 * K)
-    check(lib.pekf_magcal_dev(K, E, evb.ptr, int(n_cal), cal.ptr, fit.ptr, st.ptr, flags & EV_F64_EVENTS, None))
+    dev = _launch_calibration(K, E, evb.ptr, n_cal, flags, None)
     check(lib.pekf_device_sync())
-    c = cal.download((K, 12), np.float64)
-    status = st.download((K,), np.int32)
-    return dict(bias=c[:, :3].copy(), W=c[:, 3:].reshape(K, 3, 3).copy(), fit=fit.download((K, 6), np.float64),
-                status=status, calibrated=status == 0, cal=cal, status_dev=st)
+    return _calibration_result(K, dev)
+
+
+def _launch_calibration(K, E, ptr, n_cal, flags, stream):
+    """pekf_magcal_dev on the first E rows of device event planes (enqueued) -> dict(cal, fit_dev, status_dev)
+    DeviceBuffers: what pekf_magcal_apply_dev reads, and what _calibration_result downloads after a sync."""
+    cal, fit, st = DeviceBuffer(96 * K), DeviceBuffer(48 * K), DeviceBuffer(4 * K)
+    check(lib.pekf_magcal_dev(K, int(E), ptr, int(n_cal), cal.ptr, fit.ptr, st.ptr, flags & EV_F64_EVENTS, stream))
+    return dict(cal=cal, fit_dev=fit, status_dev=st)
+
+
+def _calibration_result(K, dev):
+    """calibrate_magnetometer's dict from _launch_calibration's buffers (the launch has completed)."""
+    c = dev["cal"].download((K, 12), np.float64)
+    status = dev["status_dev"].download((K,), np.int32)
+    return dict(bias=c[:, :3].copy(), W=c[:, 3:].reshape(K, 3, 3).copy(),
+                fit=dev["fit_dev"].download((K, 6), np.float64), status=status, calibrated=status == 0,
+                cal=dev["cal"], status_dev=dev["status_dev"])
 
 
 def _apply_calibration(calibration, batch, n_events, ev_ptr, flags, stream=None):
     """pekf_magcal_apply_dev on device event planes (enqueued): the magnetometer events of the calibrated
-    phones become W (m - bias)."""
-    if len(calibration["status"]) != batch:
+    phones become W (m - bias).  calibration: calibrate_magnetometer's dict, or _launch_calibration's (of the
+    session's own phones, its status still on the device)."""
+    if "status" in calibration and len(calibration["status"]) != batch:
         raise ValueError("the calibration is of %d phones, the session of %d" % (len(calibration["status"]), batch))
     check(lib.pekf_magcal_apply_dev(batch, int(n_events), ev_ptr, calibration["cal"].ptr,
                                     calibration["status_dev"].ptr, flags & EV_F64_EVENTS, stream))
@@ -546,8 +560,9 @@ def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", ev
     return out
 
 
-def wire_events(frames, stream=None, frame_rows=False):
-    """The clients' 100-byte wire frames -> FP64 event planes on the device (pekf_wire_events_ext_dev).
+def wire_events(frames, stream=None, frame_rows=False, phase1=False):
+    """The clients' 100-byte wire frames -> FP64 event planes on the device (pekf_wire_events_ext_dev;
+    phase1: pekf_wire_events_p1_dev).
 
     frames: [n_frames][batch][100] uint8 (wire.frames) as a host array or a (DeviceBuffer, n_frames,
     batch) triple.  Returns dict(ev2, ev3 DeviceBuffers [n_frames][batch] double4, E2 / E3 the rows a
@@ -555,7 +570,11 @@ def wire_events(frames, stream=None, frame_rows=False):
     n2 / n3 (batch,) int32 messages per phase, first_t2 DeviceBuffer (batch,) int64 (phase 2's t_start);
     with frame_rows, ev2's first E2 rows and ev3's E3 rows from row ev3_from hold every message).
     frame_rows (PEKF_WIRE_FRAME_ROWS): row f of each plane is frame f's message of that phase or the
-    no-message event (for phones whose rows would drift apart; the consumers skip those rows).  Raises
+    no-message event (for phones whose rows would drift apart; the consumers skip those rows).
+    phase1: the phase-1 messages too, every one whatever its Type (calibrate_magnetometer's samples) -- the
+    dict also has ev1 DeviceBuffer [n_frames][batch] double4, E1 the rows that hold them (ev1's first E1:
+    the most phase-1 messages of any phone, or with frame_rows 1 + the last row holding one) and n1
+    (batch,) int32; everything else is as without it, bit for bit.  Raises
     if a phone's frame is not in the client's form (wire.parse on the host reads any form std::stod
     does)."""
     if isinstance(frames, tuple):
@@ -570,25 +589,38 @@ def wire_events(frames, stream=None, frame_rows=False):
     ev2, ev3 = DeviceBuffer(32 * max(F, 1) * K), DeviceBuffer(32 * max(F, 1) * K)
     t2b, n2b, n3b, badb = DeviceBuffer(8 * K), DeviceBuffer(4 * K), DeviceBuffer(4 * K), DeviceBuffer(4 * K)
     errb = DeviceBuffer(4).upload(np.zeros(1, np.int32))
-    bounds = DeviceBuffer(8)
-    check(lib.pekf_wire_events_ext_dev(K, F, fb.ptr, F, F, ev2.ptr, ev3.ptr, t2b.ptr, n2b.ptr, n3b.ptr, badb.ptr,
-                                       errb.ptr, bounds.ptr if frame_rows else None,
-                                       WIRE_FRAME_ROWS if frame_rows else 0, stream))
+    bounds = DeviceBuffer(12)
+    if phase1:
+        ev1, n1b = DeviceBuffer(32 * max(F, 1) * K), DeviceBuffer(4 * K)
+        check(lib.pekf_wire_events_p1_dev(K, F, fb.ptr, F, F, F, ev1.ptr, ev2.ptr, ev3.ptr, t2b.ptr, n1b.ptr,
+                                          n2b.ptr, n3b.ptr, badb.ptr, errb.ptr, bounds.ptr if frame_rows else None,
+                                          WIRE_FRAME_ROWS if frame_rows else 0, stream))
+    else:
+        check(lib.pekf_wire_events_ext_dev(K, F, fb.ptr, F, F, ev2.ptr, ev3.ptr, t2b.ptr, n2b.ptr, n3b.ptr, badb.ptr,
+                                           errb.ptr, bounds.ptr if frame_rows else None,
+                                           WIRE_FRAME_ROWS if frame_rows else 0, stream))
     check(lib.pekf_device_sync() if stream is None else lib.pekf_stream_sync(stream))
     n2, n3 = n2b.download((K,), np.int32), n3b.download((K,), np.int32)
     if int(errb.download((1,), np.int32)[0]) & 1:
         bad = badb.download((K,), np.int32)
         k = int(np.argmax(bad >= 0))
         raise ValueError("phone %d, frame %d: not in the client's message form (wire.parse reads it)" % (k, bad[k]))
-    if frame_rows:  # the rows that hold messages of any phone: ev2's first E2, ev3's from row F - E3
-        E2, E3 = (int(v) for v in bounds.download((2,), np.int32))
+    n1 = n1b.download((K,), np.int32) if phase1 else None
+    if frame_rows:  # the rows that hold messages of any phone: ev2's first E2, ev3's from row F - E3, ev1's first E1
+        bw = bounds.download((3 if phase1 else 2,), np.int32)
+        E2, E3, E1 = int(bw[0]), int(bw[1]), int(bw[2]) if phase1 else 0
     else:
         E2, E3 = int(n2.max(initial=0)), int(n3.max(initial=0))
-    return dict(ev2=ev2, ev3=ev3, E2=E2, E3=E3, ev3_from=F - E3 if frame_rows else 0, n2=n2, n3=n3,
-                first_t2=t2b, frames=fb)
+        E1 = int(n1.max(initial=0)) if phase1 else 0
+    out = dict(ev2=ev2, ev3=ev3, E2=E2, E3=E3, ev3_from=F - E3 if frame_rows else 0, n2=n2, n3=n3,
+               first_t2=t2b, frames=fb)
+    if phase1:
+        out.update(ev1=ev1, E1=E1, n1=n1)
+    return out
 
 
-def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_rows=True, calibration=None):
+def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_rows=True, calibration=None,
+                     n_cal=100):
     """A whole client session from the clients' wire frames, on the device end to end (KFS/Server.cpp's
     recv'd frames -> Parser.cpp:28-72): pekf_wire_events_ext_dev (the server's parse into FP64 event
     planes), pekf_frontend_init_ext_dev (phase 2) and pekf_live_ext_dev (phase 3 + the filter) on the
@@ -597,18 +629,27 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     wire_events), whose stores stay coalesced when the phones' phase-1 / phase-2 parts differ in length
     and whose frames a small batch splits over several waves; phase 2 and phase 3 read only the rows that
     hold messages (65,536 phones: 5.0 ms against 6.0 compacted with aligned rows, 5.0 against 8.0 ms with
-    rows 64 apart).  calibration: as run_session (the phones' phase-1 frames are skipped by the device
-    parse: calibrate from wire.events_from_wire(texts, ..., phase=1)).  Raises ValueError, before anything
-    is launched, if filters.batch is not the frames' phone count."""
+    rows 64 apart).  calibration: as run_session (a dict: calibrate_magnetometer's, made elsewhere), or
+    "frames": phase 1 from the same frames, on the device and on the session's stream -- the parse keeps the
+    phase-1 messages (pekf_wire_events_p1_dev), pekf_magcal_dev fits each phone's first n_cal of them wherever
+    they sit in its stream, and pekf_magcal_apply_dev corrects the whole of phases 2 and 3; the returned dict
+    then also has calibration, the dict calibrate_magnetometer returns.  The only host round trip is
+    wire_events' own (the error word and the bounds).  Raises ValueError, before anything is launched, if
+    filters.batch is not the frames' phone count or calibration is another string."""
     K = filters.batch
+    from_frames = isinstance(calibration, str)
+    if from_frames and calibration != "frames":
+        raise ValueError("calibration must be None, calibrate_magnetometer's dict or 'frames'")
     if isinstance(frames, tuple):
         Kf = int(frames[2])
     else:
         Kf = np.shape(frames)[1] if np.ndim(frames) == 3 else K  # (wire_events refuses any other shape)
     if Kf != K:  # the planes' column stride is the frames' phone count: any other batch reads them wrong
         raise ValueError("the frames are of %d phones, the filters of %d" % (Kf, K))
-    w = wire_events(frames, stream, frame_rows)
+    w = wire_events(frames, stream, frame_rows, phase1=from_frames)
     ib, tib, rb = DeviceBuffer(48 * K), DeviceBuffer(8 * K), DeviceBuffer(4 * K)
+    if from_frames:
+        calibration = _launch_calibration(K, w["E1"], w["ev1"].ptr, n_cal, EV_F64_EVENTS, stream)
     if calibration is not None:  # with frame rows the no-message rows are walked too (and left as they are)
         _apply_calibration(calibration, K, w["E2"], w["ev2"].ptr, EV_F64_EVENTS, stream)
         _apply_calibration(calibration, K, w["E3"], w["ev3"].ptr + 32 * K * w["ev3_from"], EV_F64_EVENTS, stream)
@@ -622,6 +663,8 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     check(lib.pekf_device_sync() if stream is None else lib.pekf_stream_sync(stream))
     out = dict(ready=rb.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
                refs=refs.download((K, 6), np.float64))
+    if from_frames:
+        calibration = out["calibration"] = _calibration_result(K, calibration)
     if calibration is not None:
         out["calibrated"] = np.asarray(calibration["calibrated"], bool).copy()
     return out

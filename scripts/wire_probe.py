@@ -5,6 +5,14 @@ client text, 1,024 generated phones' phase-3 streams tiled x256), then the devic
 line: kernel ms (HIP events, median of reps), frames/s, GB/s of frames read + events written.
 
 usage: python3 scripts/wire_probe.py [reps] [--session] [--tile T (phones = 1,024 T; default 256)] [--drift D] [--phones K (at most 1,024 T)] [--rows] [--no-check]
+       python3 scripts/wire_probe.py [reps] --phase1 [--session] [--tile T]
+
+--phase1: the phase-1 form.  Every phone's stream starts with 101 calibration frames, and the same frames are
+parsed with and without the phase-1 plane (pekf_wire_events_p1_dev against pekf_wire_events_ext_dev), compacted
+and with frame rows, in one process, interleaved A/B/B/A: one JSON line per layout.  With --session: the wall
+clock of engine.run_wire_session(calibration="frames") against the route through the host parse of phase 1
+(wire.events_from_wire -> calibrate_magnetometer -> run_wire_session(calibration=dict)) on 65,536 phones x
+(101 + 700 + 1,024) frames, interleaved the same way.
 """
 from __future__ import annotations
 
@@ -143,8 +151,142 @@ def session(reps):
                           records=int(cnt.download((K,), np.int32).sum()))))
 
 
+N_CAL = 100  # the server's: message 101 fires the fit
+
+
+def _calibration_texts(K0, seed):
+    """K0 phones' phase-1 parts: N_CAL + 1 magnetometer messages each."""
+    ph1 = synth.generate_calibration_events(K0, N_CAL + 1, seed=seed)
+    return [wire.events_text(ph1["types"][:, k], ph1["values"][:, k], ph1["times"][:, k], phase=1) for k in range(K0)]
+
+
+def _abba(reps, a, b):
+    """a, b, b, a, ... (reps rounds of four after one untimed round): the two lists of results."""
+    a(), b()
+    ra, rb = [], []
+    for _ in range(reps):
+        ra.append(a()), rb.append(b()), rb.append(b()), ra.append(a())
+    return ra, rb
+
+
+def phase1(reps):
+    """262,144 phones x (101 phase-1 + 1,024 phase-3) frames: the parse with the phase-1 plane against the
+    parse without it, on the same frames, both layouts."""
+    tile = int(sys.argv[sys.argv.index("--tile") + 1]) if "--tile" in sys.argv else 256
+    K0, E, E1 = 1024, 1024, N_CAL + 1
+    t0 = time.time()
+    ev = synth.generate_events(np.arange(K0), E, seed=5)
+    cal = _calibration_texts(K0, 9)
+    texts = [cal[k] + wire.events_text(ev["types"][:, k], ev["values"][:, k], ev["times"][:, k]) for k in range(K0)]
+    fr = np.ascontiguousarray(np.tile(wire.frames(texts), (1, tile, 1)))
+    gen_s = time.time() - t0
+    F, K = fr.shape[:2]
+    fb = engine.DeviceBuffer(fr.nbytes).upload(fr)
+    del fr
+    ev1, ev2, ev3 = (engine.DeviceBuffer(32 * F * K) for _ in range(3))
+    t2b, n1b, n2b, n3b = (engine.DeviceBuffer(8 * K), engine.DeviceBuffer(4 * K), engine.DeviceBuffer(4 * K),
+                          engine.DeviceBuffer(4 * K))
+    errb = engine.DeviceBuffer(4).upload(np.zeros(1, np.int32))
+    bounds = engine.DeviceBuffer(12)
+    st = engine.Stream()
+    e0, e1 = engine.Event(), engine.Event()
+    want1 = synth.pack_events64(wire.events_from_wire(texts[:1], np.zeros((1, 3)), np.zeros((1, 3)), [0], phase=1))
+    want3 = synth.pack_events64(wire.events_from_wire(texts[:1], np.zeros((1, 3)), np.zeros((1, 3)), [0]))
+    for rows in (False, True):
+        flags = 1 if rows else 0
+        m1, m2, m3 = (F, F, F) if rows else (E1, 0, E)     # compacted: the rows the messages need, no padding rows
+
+        def timed(call):
+            e0.record(st.handle)
+            check(call())
+            e1.record(st.handle)
+            e1.sync()
+            return e0.elapsed_ms(e1)
+
+        def without():
+            return timed(lambda: lib.pekf_wire_events_ext_dev(
+                K, F, fb.ptr, m2, m3, ev2.ptr, ev3.ptr, t2b.ptr, n2b.ptr, n3b.ptr, None, errb.ptr,
+                bounds.ptr if rows else None, flags, st.handle))
+
+        def with_plane():
+            return timed(lambda: lib.pekf_wire_events_p1_dev(
+                K, F, fb.ptr, m1, m2, m3, ev1.ptr, ev2.ptr, ev3.ptr, t2b.ptr, n1b.ptr, n2b.ptr, n3b.ptr, None, errb.ptr,
+                bounds.ptr if rows else None, flags, st.handle))
+
+        ms0, ms1 = _abba(reps, without, with_plane)
+        with_plane()  # (the planes checked below are this entry's)
+        assert int(errb.download((1,), np.int32)[0]) == 0
+        assert np.all(n1b.download((K,), np.int32) == E1) and np.all(n3b.download((K,), np.int32) == E)
+        for buf, want, m in ((ev1, want1, m1), (ev3, want3, m3)):  # spot check: phone 0 and a tiled copy of it
+            got = buf.download((m, K, 4), np.float64)[:, [0, K0 * 7]]
+            keep = got[:, 0, 3:4].view(np.uint64)[:, 0] != np.uint64(synth.EV64_NONE_W)
+            assert np.array_equal(got[keep][:, 0].view(np.uint64), want[:, 0].view(np.uint64))
+            assert np.array_equal(got[keep][:, 1].view(np.uint64), want[:, 0].view(np.uint64))
+        m0, m1 = float(np.median(ms0)), float(np.median(ms1))
+        print(json.dumps(dict(kernel="k_wire_events, P1 = true against P1 = false", phones=K, frames_per_phone=F,
+                              phase1_frames=E1, frame_rows=rows, without_ms=m0, with_ms=m1, ratio=m1 / m0,
+                              ms_without=ms0, ms_with=ms1,
+                              bytes_per_frame="100 read + " + ("96 written (without: 64)" if rows else
+                                                               "32 written per message (without: per phase-3 one)"),
+                              text_gen_s=gen_s)), flush=True)
+
+
+def phase1_session(reps):
+    """65,536 phones x (101 + 700 + 1,024) frames, wall clock: run_wire_session(calibration="frames") against
+    the route through the host parse of phase 1.  The frames are on the device before either starts."""
+    K0, tile, E2, E3 = 1024, 64, 700, 1024
+    ph2 = synth.generate_events(np.arange(K0), E2, seed=71)
+    ph3 = synth.generate_events(np.arange(K0), E3, seed=72)
+    ph3 = dict(ph3, times=ph3["times"] - ph3["t_init"][None, :] + ph2["times"][-1][None, :])
+    cal = _calibration_texts(K0, 73)
+    texts = [cal[k] + wire.events_text(ph2["types"][:, k], ph2["values"][:, k], ph2["times"][:, k], phase=2) +
+             wire.events_text(ph3["types"][:, k], ph3["values"][:, k], ph3["times"][:, k], phase=3) for k in range(K0)]
+    fr = np.ascontiguousarray(np.tile(wire.frames(texts), (1, tile, 1)))
+    F, K = fr.shape[:2]
+    frames = (engine.DeviceBuffer(fr.nbytes).upload(fr), F, K)
+    del fr
+    all_texts = [t.encode() for t in texts] * tile        # every phone's text, as the host route parses it
+    f = engine.BatchedEKF(K)
+    st = engine.Stream()
+    last = {}
+
+    def device_route():
+        f.reset()
+        check(lib.pekf_device_sync())
+        t = time.perf_counter()
+        last["dev"] = engine.run_wire_session(frames, f, stream=st.handle, calibration="frames", n_cal=N_CAL)
+        return time.perf_counter() - t
+
+    def host_route():
+        f.reset()
+        check(lib.pekf_device_sync())
+        t = time.perf_counter()
+        e1 = wire.events_from_wire(all_texts, np.zeros((K, 3)), np.zeros((K, 3)), np.zeros(K, np.int64), phase=1)
+        t_parse = time.perf_counter() - t
+        c = engine.calibrate_magnetometer(e1, n_cal=N_CAL, events="f64")
+        last["host"] = dict(engine.run_wire_session(frames, f, stream=st.handle, calibration=c), calibration=c)
+        last["parse_s"] = t_parse
+        return time.perf_counter() - t
+
+    dev_s, host_s = _abba(reps, device_route, host_route)
+    a, b = last["dev"], last["host"]
+    assert a["calibrated"].all() and a["ready"].all()
+    for key in ("ready", "counts", "refs", "calibrated"):
+        assert np.array_equal(a[key], b[key]), key
+    for key in ("bias", "W", "fit", "status"):
+        assert np.array_equal(a["calibration"][key], b["calibration"][key]), key
+    d, h = float(np.median(dev_s)), float(np.median(host_s))
+    print(json.dumps(dict(kernel="wire session with phase 1", phones=K, frames_per_phone=F,
+                          device_route_s=d, host_route_s=h, host_parse_s=last["parse_s"], ratio=h / d,
+                          s_device_route=dev_s, s_host_route=host_s,
+                          records=int(a["counts"].sum()))), flush=True)
+
+
 if __name__ == "__main__":
-    if "--session" in sys.argv:
+    if "--phase1" in sys.argv:
+        n = int(sys.argv[1]) if sys.argv[1:2] and sys.argv[1].isdigit() else 3
+        (phase1_session if "--session" in sys.argv else phase1)(n)
+    elif "--session" in sys.argv:
         session(int(sys.argv[1]) if sys.argv[1:2] and sys.argv[1].isdigit() else 5)
     else:
         main()
