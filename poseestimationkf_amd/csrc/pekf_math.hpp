@@ -610,80 +610,36 @@ PEKF_DEV void quat_to_rotm(const double *q, double *M) {
     M[6] = 2.0 * (x * z - w * y);       M[7] = 2.0 * (y * z + w * x);       M[8] = 1.0 - 2.0 * (x * x + y * y);
 }
 
-// Y' = q_W^* (x) Y for the flipped Wahba quaternion Y of the weights (ka, km), in the reference
-// frame's basis (z' the prediction in that basis): Y' = v * sc.  As rotm_to_quat_toward, with its
-// |q.z| < 1/4 fallback taken in the world basis (R = Fw R', z = q_W (x) z') so that it is the
-// reference's own branch formula and flip.  There is no near-identity fallback here: within
+struct NoPin {
+    PEKF_DEV void operator()() const {}
+};
+// The matrix chain: the current frame Fv, R' = Rz(theta) Fv^T, Q4 = I + K(R') and v = Q4 z (as
+// rotm_to_quat_toward).  It is the fallback body of wahba_toward_from_product below (behind PEKF_TAKEN
+// there), for the lanes the product form does not serve: a measurement more than ~150 degrees from the
+// prediction, a negative magnetometer weight and a NaN (degenerate) frame.  reload(acc, mag): the
+// record's samples again; the caller re-reads them (memory, LDS).
+// Where |q.z| < 1/4 it takes the reference's own branch formula and flip in the world basis (R = Fw R',
+// z = q_W (x) z').  There is no near-identity fallback here: within
 // ~1e-5 rad of the identity the reference's formula divides rounding noise by ~theta, so its
 // result differs from ANY other evaluation of the same rotation by ~1e-16/theta (ours included,
 // whatever formula we use: R' and numpy's SVD rotation differ in the last bits), and an exactly
 // identity world rotation -- the one input where it is deterministic (NaN) -- does not arise from
 // Fw R'.  The well-conditioned Q4 z value is returned instead.
-struct NoPin {
-    PEKF_DEV void operator()() const {}
-};
-// pin(): called after v = Q4 z and before the fallback branch (see ekf_record_step's PEKF_PIN_SCHUR)
-// reload(acc, mag): the record's samples again, for a degenerate current frame only (a zero sample or acc
-// parallel to mag, rank-1 B): V is NaN there, so is nv, and the fallback branch -- taken for NaN too --
-// solves Wahba by wahba_current_rank1_quat with the reference's weights |acc_z|, 1 - |acc_z|
-// (ExtendedKalmanFilter.py:71).  The caller re-reads them (memory, LDS) instead of holding six doubles
-// in registers through the Wahba chain.
-// wahba_quat_toward (below) in two halves, for ekf_record_step's HOIST schedule (the same arithmetic;
-// the one-piece form is kept for every other kernel, whose schedule it fixes).
-// The state-independent half: Wahba's rotation R' of the current frame in the reference basis (it
-// depends on the record's samples only, not on the prediction z).
-template <int F = 1, class RW, std::enable_if_t<RW::kRefBasis, int> = 0>
-PEKF_DEV void wahba_rotation_ref(const RW &W, const Frame &V, double ka, double km, double *R) {
-    const double kw = km * W.b2W, kb = km * W.b1W;
-    double p = ka * W.aW * V.alpha + kb * V.beta1 + kw * V.beta2;
-    double s = kw * V.beta1 - kb * V.beta2;
-    const double ih = rsqrt<F>(p * p + s * s);
-    p *= ih;
-    s *= ih;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        R[j] = p * V.e1[j] - s * V.e2[j];
-        R[3 + j] = s * V.e1[j] + p * V.e2[j];
-        R[6 + j] = V.u3[j];
+// A degenerate current frame (a zero sample or acc parallel to mag, rank-1 B) makes V NaN, so nv too:
+// Wahba is solved by wahba_current_rank1_quat with the reference's weights |acc_z|, 1 - |acc_z|
+// (ExtendedKalmanFilter.py:71).
+template <int F = 1, class RW, class Reload, std::enable_if_t<RW::kRefBasis, int> = 0>
+PEKF_DEV void wahba_matrix_toward(const RW &W, const Reload &reload, const double *z, double *v, double &sc) {
+    Frame V;
+    double ka, km;
+    {
+        double acc[3], mag[3];
+        reload(acc, mag);
+        ka = fabs(acc[2]);  // (ExtendedKalmanFilter.py:71) again, not held across the branch
+        km = 1.0 - ka;
+        // ka = |acc_z| >= 0, so wahba_sign(ka, km) is the sign of km = 1 - ka (never -0)
+        make_frame<F>(acc, mag, V, km);
     }
-}
-
-// The z-dependent half: Q4 of R' flipped toward z, with the fallbacks.
-template <int F = 1, class RW, class Reload, class Pin = NoPin, std::enable_if_t<RW::kRefBasis, int> = 0>
-PEKF_DEV void wahba_toward_from_rotation(const RW &W, const double *R, const double *z, double *v, double &sc,
-                                         const Reload &reload, const Pin &pin = Pin()) {
-    double nv, t0;
-    q4_times(R, z, v, nv, t0);
-    sc = rsqrt<F>(nv);
-    pin();
-    if (PEKF_TAKEN(!(nv >= 1.0), false)) {  // (nv < 1, or NaN)
-        double Fw[9], Rw[9], zw[4], vw[4], qw[4];
-        W.quat(qw);
-        quat_to_rotm(qw, Fw);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Rw[3 * i + j] = Fw[3 * i] * R[j] + Fw[3 * i + 1] * R[3 + j] + Fw[3 * i + 2] * R[6 + j];
-        qmul_left<false>(qw, z, zw);
-        rotm_to_quat_flip_reference(Rw, zw, vw, sc);
-        qmul_left<true>(qw, vw, v);
-        // NaN: a degenerate current frame.  In this basis B' = Fw^T B pairs acc, mag with the reference
-        // pair's own coordinates (aW, 0, 0), (b1W, b2W, 0); its shortest-arc attitude, flipped toward z
-        // as ExtendedKalmanFilter.py:73-75 flips, replaces the NaN one.
-        if (!(nv == nv)) {  // (it overwrites v and sc in place)
-            double acc[3], mag[3];
-            reload(acc, mag);
-            const double a0[3] = {W.aW, 0.0, 0.0}, m0[3] = {W.b1W, W.b2W, 0.0}, kr = fabs(acc[2]);
-            wahba_current_rank1_quat<1>(a0, m0, acc, mag, kr, 1.0 - kr, v);
-            sc = v[0] * z[0] + v[1] * z[1] + v[2] * z[2] + v[3] * z[3] < 0.0 ? -1.0 : 1.0;
-        }
-    }
-    (void)t0;
-}
-
-template <int F = 1, class RW, class Reload, class Pin = NoPin, std::enable_if_t<RW::kRefBasis, int> = 0>
-PEKF_DEV void wahba_quat_toward(const RW &W, const Frame &V, double ka, double km, const double *z, double *v,
-                                double &sc, const Reload &reload, const Pin &pin = Pin()) {
     const double kw = km * W.b2W, kb = km * W.b1W;
     double p = ka * W.aW * V.alpha + kb * V.beta1 + kw * V.beta2;
     double s = kw * V.beta1 - kb * V.beta2;
@@ -700,8 +656,7 @@ PEKF_DEV void wahba_quat_toward(const RW &W, const Frame &V, double ka, double k
     double nv, t0;
     q4_times(R, z, v, nv, t0);
     sc = rsqrt<F>(nv);
-    pin();
-    if (PEKF_TAKEN(!(nv >= 1.0), false)) {  // (nv < 1, or NaN)
+    if (!(nv >= 1.0)) {  // (nv < 1, or NaN)
         double Fw[9], Rw[9], zw[4], vw[4], qw[4];
         W.quat(qw);
         quat_to_rotm(qw, Fw);
@@ -717,13 +672,99 @@ PEKF_DEV void wahba_quat_toward(const RW &W, const Frame &V, double ka, double k
         // as ExtendedKalmanFilter.py:73-75 flips, replaces the NaN one.
         if (!(nv == nv)) {  // (it overwrites v and sc in place)
             double acc[3], mag[3];
-            reload(acc, mag);
+            reload(acc, mag);  // (once more, rather than six doubles held through the branch above)
             const double a0[3] = {W.aW, 0.0, 0.0}, m0[3] = {W.b1W, W.b2W, 0.0}, kr = fabs(acc[2]);
             wahba_current_rank1_quat<1>(a0, m0, acc, mag, kr, 1.0 - kr, v);
             sc = v[0] * z[0] + v[1] * z[1] + v[2] * z[2] + v[3] * z[3] < 0.0 ? -1.0 : 1.0;
         }
     }
     (void)t0;
+}
+
+// Y' = q_W^* (x) Y for the flipped Wahba quaternion Y of the weights (ka, km), in the reference frame's
+// basis (z' the prediction in that basis): Y' = v * sc.  Only the quaternion of R' = Rz(theta) Fv^T is
+// wanted, up to a scale and with the sign of q.z, and R' is a product of three plane rotations whose
+// unnormalised half-angle quaternions come from numbers the frame's Gram-Schmidt forms anyway, so no
+// frame, matrix or Q4 is built:
+//   q_A  the shortest arc taking acc to the x axis:        (|a| + a_x, 0, a_z, -a_y)
+//   q_B  about x, taking t' = A (mag - beta1 e1) to y:     (|t'| + t'_y, -t'_z, 0, 0)
+//   q_th about z by theta, (cos, sin) ~ (p, s):            (h + p, 0, 0, s), h = |(p, s)|
+// and q' ~ q_th (x) q_B (x) q_A.  t' needs no t: A m = m - (e1 + x) (beta1 + m_x) / (1 + e1_x) + 2 beta1 x,
+// whose y and z components, scaled by w = |a| + a_x, are w m_y - a_y u and w m_z - a_z u, u = beta1 + m_x;
+// |t'| w = beta2 w, and (p, s) is taken at the same scale w (alpha w, beta1 w, beta2 w).
+// Conditioning.  A half-angle form (1 + cos, sin) cancels near a half turn: its angle error is
+// (eps / 2) tan(phi / 2).  The attitude of a moving body takes every value, so on a real stream some
+// lane of a wave is always near a half turn of q_A or q_B (1 + cos < 1/8 on 6 % and 16 % of the
+// records of the synthetic stream: a branch to another form there would be taken by every wave at
+// every record).  So each arc is taken in the half where it is well conditioned, by selects:
+//   q_A  sigma = sign(a_x): the pair (sigma a, sigma m) has the frame Fv diag(sigma, sigma, 1), i.e.
+//        Fv^T = Rz(pi)^[sigma < 0] Fv_sigma^T, and the half turn about z adds to theta: (p, s) ->
+//        sigma (p, s).  Every sigma below is the sign bit of a_x copied onto a factor that is formed
+//        anyway (1/|a|, 1/|t'|), and q_A is used times sigma: (sigma w, 0, a_z, -a_y), w = |a| + |a_x|.
+//   q_B, q_th  a plane rotation (C, S) of length H has the half-angle quaternion (H + C, S) and, up to a
+//        factor S / (H + C), (S, H - C): the first for C >= 0, the second for C < 0, so that the sum is
+//        H + |C| >= H in both (arcs of at most a quarter turn: angle error <= eps / 2).
+// The factor's sign is free: the result takes the sign of q'.z at the end.
+// The state-independent half (it depends on the record's samples only, not on the prediction z), for
+// ekf_record_step's HOIST schedule: q' unnormalised.  km < 0 (|acc_z| > 1, the reflection case of
+// wahba_sign) is not handled here: wahba_toward_from_product sends it to the matrix chain.
+template <int F = 1, class RW, std::enable_if_t<RW::kRefBasis, int> = 0>
+PEKF_DEV void wahba_product_ref(const RW &W, const double *a, const double *m, double ka, double km, double *q) {
+    const double sa = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
+    const double ias = copysign(rsqrt<F>(sa), a[0]);
+    const double nas = sa * ias;                                            // sigma |a|
+    const double ws = nas + a[0];                                           // sigma w
+    const double b1s = (a[0] * m[0] + a[1] * m[1] + a[2] * m[2]) * ias;     // sigma beta1
+    const double us = b1s + m[0];                                           // sigma u
+    const double tys = ws * m[1] - a[1] * us;                               // w t'_y of (sigma a, sigma m)
+    const double ntz = a[2] * us - ws * m[2];                               // -w t'_z
+    const double sb = tys * tys + ntz * ntz;
+    const double hs = sb * copysign(rsqrt<F>(sb), a[0]);                    // sigma beta2 w
+    const double kw = km * W.b2W, kb = km * W.b1W;
+    const double aw = fabs(nas) * ws, b1w = b1s * fabs(ws);                 // sigma alpha w, sigma beta1 w
+    const double p = ka * W.aW * aw + kb * b1w + kw * hs;                   // sigma w (p, s) of wahba_rotation
+    const double s = kw * b1w - kb * hs;
+    const double n = p * p + s * s;
+    const double h = n * rsqrt<F>(n);
+    const double wt = h + fabs(p), wb = fabs(hs) + fabs(tys);
+    const bool ft = p >= 0.0, fb = tys >= 0.0;
+    const double c0 = ft ? wt : s, c3 = ft ? s : wt;                        // q_th = (c0, 0, 0, c3)
+    const double b0 = fb ? wb : ntz, b1 = fb ? ntz : wb;                    // q_B = (b0, b1, 0, 0)
+    // r = q_B (x) sigma q_A, then q' = q_th (x) r
+    const double r0 = b0 * ws, r1 = b1 * ws, r2 = b0 * a[2] + b1 * a[1], r3 = b1 * a[2] - b0 * a[1];
+    q[0] = c0 * r0 - c3 * r3;
+    q[1] = c0 * r1 - c3 * r2;
+    q[2] = c0 * r2 + c3 * r1;
+    q[3] = c0 * r3 + c3 * r0;
+}
+
+// The z-dependent half: q' scaled to unit length with the sign of q'.z, and the fallback to the matrix
+// chain where |q'.z| < |q'| / 4 (as nv < 1 of Q4 z: the measured attitude more than ~150 degrees from the
+// prediction), km < 0 or NaN (a degenerate frame).  None occurs on a tracked stream, so the fallback
+// costs a wave nothing unless one of its lanes needs it.
+// pin(): called before the fallback branch (see ekf_record_step's PEKF_PIN_SCHUR).
+// reload(acc, mag): the record's samples again, for the fallback only.  The caller re-reads them (memory,
+// LDS) instead of holding six doubles in registers to the end of the chain.
+template <int F = 1, class RW, class Reload, class Pin = NoPin, std::enable_if_t<RW::kRefBasis, int> = 0>
+PEKF_DEV void wahba_toward_from_product(const RW &W, const double *q, double km, const double *z,
+                                        double *v, double &sc, const Reload &reload, const Pin &pin = Pin()) {
+    const double c = fma(q[0], z[0], fma(q[1], z[1], fma(q[2], z[2], q[3] * z[3])));
+    const double nq = fma(q[0], q[0], fma(q[1], q[1], fma(q[2], q[2], q[3] * q[3])));
+    sc = copysign(rsqrt<F>(nq), c);
+    v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    pin();
+    if (PEKF_TAKEN(!(c * sc >= 0.25) || !(km >= 0.0), false)) {  // (NaN too)
+        wahba_matrix_toward<F>(W, reload, z, v, sc);
+    }
+}
+
+// Both halves in one piece (every schedule but HOIST)
+template <int F = 1, class RW, class Reload, class Pin = NoPin, std::enable_if_t<RW::kRefBasis, int> = 0>
+PEKF_DEV void wahba_quat_toward(const RW &W, const double *acc, const double *mag, double ka, double km,
+                                const double *z, double *v, double &sc, const Reload &reload, const Pin &pin = Pin()) {
+    double q[4];
+    wahba_product_ref<F>(W, acc, mag, ka, km, q);
+    wahba_toward_from_product<F>(W, q, km, z, v, sc, reload, pin);
 }
 
 // Y = v * sc in the world basis (the per-record kernels)

@@ -243,12 +243,12 @@ __device__ __forceinline__ void record_correct(double *x, const double *z, Sym4T
     }
 }
 
-// HOIST (the FP64 multi-record loop only): the Correction's state-independent half -- S^-1, the
-// current frame and Wahba's rotation R' -- is formed ahead of the missing-magnetometer branch, in the
+// HOIST (the FP64 multi-record loop only): the Correction's state-independent half -- S^-1 and
+// Wahba's unnormalised quaternion q' -- is formed ahead of the missing-magnetometer branch, in the
 // Prediction's basic block (held there by an empty asm), so one block carries two independent
-// dependency chains (the Prediction's and the record's own); only Q4 z, its flip and the update stay
-// behind the branch.  For launches of at most one wave per SIMD (config 2), where nothing else fills
-// the chain's stalls (launch_run_multi selects it).  The same arithmetic, bit for bit.
+// dependency chains (the Prediction's and the record's own); only q'.z, its scale and flip and the
+// update stay behind the branch.  For launches of at most one wave per SIMD (config 2), where nothing
+// else fills the chain's stalls (launch_run_multi selects it).  The same arithmetic, bit for bit.
 template <typename PT, bool MC = false, bool LAZY = false, bool OM = false, bool PIN = false, bool HOIST = false,
           typename Ref, typename Reload>
 __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> &P, const Ref &Wf, const StepK<PT> &k,
@@ -286,18 +286,16 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> 
     if constexpr (HOIST) {
         const Sym4T<PT> Si = spd_inverse_schur<PT, true, MC>(S2);
         const double ka = fabs(acc[2]);              // (:71)
-        Frame Vf;
-        make_frame<F>(acc, mag, Vf, 1.0 - ka);
-        double R[9];
-        wahba_rotation_ref<F>(Wf, Vf, ka, 1.0 - ka, R);
+        double qm[4];
+        wahba_product_ref<F>(Wf, acc, mag, ka, 1.0 - ka, qm);
         asm volatile("" ::"v"(Si.a00), "v"(Si.a01), "v"(Si.a02), "v"(Si.a03), "v"(Si.a11), "v"(Si.a12),
-                     "v"(Si.a13), "v"(Si.a22), "v"(Si.a23), "v"(Si.a33), "v"(R[0]), "v"(R[1]), "v"(R[2]),
-                     "v"(R[3]), "v"(R[4]), "v"(R[5]), "v"(R[6]), "v"(R[7]), "v"(R[8]));
+                     "v"(Si.a13), "v"(Si.a22), "v"(Si.a23), "v"(Si.a33), "v"(qm[0]), "v"(qm[1]), "v"(qm[2]),
+                     "v"(qm[3]));
         if (missing) {
             record_skip<PT, MC>(x, z, P, S2, k);
         } else {
             double v[4], sc;
-            wahba_toward_from_rotation<F>(Wf, R, z, v, sc, reload);  // Wahba.py:8-47 + the flip of :73-75
+            wahba_toward_from_product<F>(Wf, qm, 1.0 - ka, z, v, sc, reload);  // Wahba.py:8-47 + the flip of :73-75
             record_correct<PT, MC>(x, z, P, Si, v, sc, k);
         }
         return;
@@ -318,9 +316,6 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> 
 
         // ---- Correction (ExtendedKalmanFilter.py:70-80) ----
         const double ka = fabs(acc[2]);              // (:71)
-        Frame Vf;
-        // ka = |acc_z| >= 0, so wahba_sign(ka, km) is the sign of km = 1 - ka (never -0)
-        make_frame<F>(acc, mag, Vf, 1.0 - ka);
         double v[4], sc;
         // PIN: S^-1 depends only on the Prediction; have it computed before the rare fallback branch,
         // in the basic block of the Wahba chain, so that the two independent chains interleave (left
@@ -333,7 +328,15 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> 
                 asm volatile("" ::"v"(Si.a00), "v"(Si.a01), "v"(Si.a02), "v"(Si.a03), "v"(Si.a11), "v"(Si.a12),
                              "v"(Si.a13), "v"(Si.a22), "v"(Si.a23), "v"(Si.a33));
         };
-        wahba_quat_toward<F>(Wf, Vf, ka, 1.0 - ka, z, v, sc, reload, pin);  // Wahba.py:8-47 + the flip of :73-75: Y = v sc
+        // Wahba.py:8-47 + the flip of :73-75: Y = v sc
+        if constexpr (std::is_same<Ref, Frame>::value) {
+            Frame Vf;
+            // ka = |acc_z| >= 0, so wahba_sign(ka, km) is the sign of km = 1 - ka (never -0)
+            make_frame<F>(acc, mag, Vf, 1.0 - ka);
+            wahba_quat_toward<F>(Wf, Vf, ka, 1.0 - ka, z, v, sc, reload, pin);
+        } else {
+            wahba_quat_toward<F>(Wf, acc, mag, ka, 1.0 - ka, z, v, sc, reload, pin);
+        }
         // e = Y - z (MC: D e, whose last two components are z - Y)
         const PT e0 = (PT)fma_sub(v[0], sc, z[0]), e1 = (PT)fma_sub(v[1], sc, z[1]);
         const PT e2 = (PT)(MC ? fma_rsub(v[2], sc, z[2]) : fma_sub(v[2], sc, z[2]));
