@@ -187,8 +187,10 @@ int launch_update(int64_t batch, const double *gyro, const int64_t *t_ns, const 
                   const uint8_t *missing, const double *refs, int64_t *prev_t, double *X, double *P, double q,
                   double r, double *x_out, uint32_t flags, hipStream_t stream);
 
-// Multi-record fused launches (pekf_run_multi.hip, compiled with the max-ILP scheduler): every
-// k_run<TRAJ, MIXED, SOA, COUNTS, ONE = false> variant; arguments checked by pekf_run_dev.
+// Multi-record fused launches over 40 B records (pekf_run_multi.hip, compiled with the max-ILP
+// scheduler): every k_run<Rec, TRAJ, MIXED, SOA, COUNTS, ...> variant; arguments checked by
+// pekf_run_ext_dev, which launches k_run_one itself for n_steps = 1.  (The k_run<Rec64, ...> variants
+// are launched by pekf_run_rec64_dev in the same file.)
 int launch_run_multi(int64_t batch, int64_t n_steps, int64_t window, int64_t step0, const float4 *gd,
                      const float4 *am, const float2 *my, const double *dtx, const double *refs, double *X,
                      double *P, double q, double r, double *traj, const int32_t *counts, bool mixed, bool soa,

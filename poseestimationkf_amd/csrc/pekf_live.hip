@@ -263,14 +263,7 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     double x[4];
     Sym4T<double> P;
     load_state<false>(Xio, Pio, b, batch, x, P);
-    RefWLazy Wr;
-    Wr.aW = Wf.alpha; Wr.b1W = Wf.beta1; Wr.b2W = Wf.beta2;
-    Wr.pair = refs + 6 * b;
-    {
-        double qw[4];
-        frame_quat(Wf, qw);
-        to_ref_basis(qw, x, P, rs);
-    }
+    const RefWLazy Wr = enter_ref_basis<false>(Wf, refs + 6 * b, false, x, P, rs);
     const StepK<double> kc = step_consts<double, true>(qs, rs);
 
     using Queue = std::conditional_t<EV64, LdsQueueF64<kQueue>,

@@ -742,7 +742,7 @@ PEKF_DEV void wahba_product_ref(const RW &W, const double *a, const double *m, d
 // chain where |q'.z| < |q'| / 4 (as nv < 1 of Q4 z: the measured attitude more than ~150 degrees from the
 // prediction), km < 0 or NaN (a degenerate frame).  None occurs on a tracked stream, so the fallback
 // costs a wave nothing unless one of its lanes needs it.
-// pin(): called before the fallback branch (see ekf_record_step's PEKF_PIN_SCHUR).
+// pin(): called before the fallback branch (ekf_record_step's PIN schedule, pekf_step.hpp).
 // reload(acc, mag): the record's samples again, for the fallback only.  The caller re-reads them (memory,
 // LDS) instead of holding six doubles in registers to the end of the chain.
 template <int F = 1, class RW, class Reload, class Pin = NoPin, std::enable_if_t<RW::kRefBasis, int> = 0>

@@ -50,6 +50,79 @@ __global__ __launch_bounds__(kRunBlock) void k_reset(int64_t batch, double *X, d
     tl.store(P, pv);
 }
 
+// One record per filter from the stream planes (pekf_run_dev with n_steps = 1: online serving), in
+// the world basis with the covariance as P.  The state and the reference pair are most of the
+// traffic: the AoS state and the [batch][6] reference pairs move in coalesced wave tiles
+// (pekf_tile.hpp) instead of 128 / 48 B-strided per-lane accesses; the SoA state is read and written
+// per lane, one contiguous 512 B access per component and wave.  No prefetch of a next record: its
+// 40 B would be an eighth of the traffic.  The template flags are k_run's (pekf_step.hpp).
+template <bool TRAJ, bool MIXED, bool SOA, bool COUNTS, bool LONGDT>
+__global__ __launch_bounds__(kRunBlock) void k_run_one(int64_t batch, int64_t window, int64_t step0,
+                                                       const float4 *__restrict__ gd, const float4 *__restrict__ am,
+                                                       const float2 *__restrict__ my, const double *__restrict__ refs,
+                                                       double *__restrict__ Xio, double *__restrict__ Pio, double qs,
+                                                       double rs, double *__restrict__ traj,
+                                                       const int32_t *__restrict__ counts,
+                                                       const double *__restrict__ dtx) {
+    using PT = typename std::conditional<MIXED, float, double>::type;
+    constexpr int kTile = SOA ? 6 : 16;
+    __shared__ double pool[kRunBlock / kWave * tile_doubles<kTile>()];
+    const WaveTile t(pool, tile_doubles<kTile>(), batch);
+    double cx[4], cp[16], cr[6];
+    if constexpr (!SOA) {
+        t.gather(Xio, cx);
+        t.gather(Pio, cp);
+    }
+    t.gather(refs, cr);
+    const bool act = t.active();
+    const uint32_t lane = act ? (uint32_t)(t.first + t.lane) : 0u;  // idle lanes read a valid row
+    const int64_t base = (step0 % window) * batch;
+    const Rec cur = {(gd + base)[lane], (am + base)[lane], (my + base)[lane]};
+    const bool run = act && (!COUNTS || counts[lane] > 0);
+    double x[4], pv[16], rf[6];
+    Sym4T<PT> P;
+    if constexpr (SOA) {
+        load_state<true>(Xio, Pio, lane, batch, x, P);
+    } else {
+        t.to_lanes(cx, x);
+        t.to_lanes(cp, pv);
+        P = sym_from16<PT>(pv);
+    }
+    t.to_lanes(cr, rf);
+    Frame Wf;
+    make_frame<true>(rf, rf + 3, Wf);
+    if (run) {
+        const double gy[3] = {cur.gd.x, cur.gd.y, cur.gd.z};
+        const uint32_t word = __float_as_uint(cur.gd.w);
+        const double acc[3] = {cur.am.x, cur.am.y, cur.am.z};
+        const double mag[3] = {cur.am.w, cur.my.x, cur.my.y};
+        double dtn = (double)(word & PEKF_DT_MASK);
+        if constexpr (LONGDT) {
+            if ((word & PEKF_DT_MASK) == PEKF_DT_ESCAPE) dtn = (dtx + base)[lane];
+        }
+        auto reload = [&](double *a, double *m) {  // rare: the degenerate-Wahba fallback
+            const float4 va = (am + base)[lane];
+            const float2 vm = (my + base)[lane];
+            a[0] = va.x; a[1] = va.y; a[2] = va.z;
+            m[0] = va.w; m[1] = vm.x; m[2] = vm.y;
+        };
+        ekf_record_step<PT>(x, state_norm2(x), P, Wf, step_consts<PT, false>(qs, rs), gy, dtn,
+                            (word & PEKF_MISSING_MAG_BIT) != 0, acc, mag, reload);
+    }
+    if (TRAJ && act) {
+        double2 *o = reinterpret_cast<double2 *>(traj) + 2 * (int64_t)lane;
+        o[0] = make_double2(x[0], x[1]);
+        o[1] = make_double2(x[2], x[3]);
+    }
+    if constexpr (SOA) {
+        if (act) store_state<true>(Xio, Pio, lane, batch, x, P);
+    } else {
+        sym_to16(P, pv);
+        t.store(Xio, x);
+        t.store(Pio, pv);
+    }
+}
+
 // One record per filter from FP64 arrays (the filter handle's online update,
 // pekf_filter_update): dt = t - previousT per filter (ExtendedKalmanFilter.py:62,67), then the
 // same ekf_record_step as the stream kernel.  Record arrays are filter-major ([batch][3]).
@@ -163,12 +236,12 @@ int pekf_run_ext_dev(int64_t batch, int64_t n_steps, int64_t window, int64_t ste
     // one-record launch (online serving)
     dispatch_bools(
         [&](auto tr, auto mx, auto so, auto cn, auto ld) {
-            hipLaunchKernelGGL((k_run<tr.value, mx.value, so.value, cn.value, true, false, ld.value>), grid, block, 0,
-                               as_stream(stream), batch, n_steps, window, step0, gd, am, my, refs, X, P, q, r, traj,
-                               counts, dt_ext);
+            hipLaunchKernelGGL((k_run_one<tr.value, mx.value, so.value, cn.value, ld.value>), grid, block, 0,
+                               as_stream(stream), batch, window, step0, gd, am, my, refs, X, P, q, r, traj, counts,
+                               dt_ext);
         },
         traj != nullptr, mixed, soa, counts != nullptr, dt_ext != nullptr);
-    return launched("k_run");
+    return launched("k_run_one");
 }
 
 int pekf_run_dev(int64_t batch, int64_t n_steps, int64_t window, int64_t step0,

@@ -1,8 +1,9 @@
 // pekf_step.hpp -- device code of the fused hot path shared by pekf_run.hip (one-record launches,
-// the filter handle's update) and pekf_run_multi.hip (multi-record launches): the record layout, the
-// state layouts, one record of main_file.py:42-45 on a lane's registers (ekf_record_step) and the
-// fused stream kernel template k_run.  The two files instantiate disjoint sets of k_run variants
-// and are compiled with different scheduling strategies (Makefile), never different arithmetic.
+// the filter handle's update), pekf_run_multi.hip (multi-record launches over 40 B and FP64 records)
+// and pekf_live.hip: the state layouts, the record planes' row cursor, one record of main_file.py:42-45
+// on a lane's registers (ekf_record_step), the change to the reference frame's basis and the
+// multi-record stream kernel template k_run.  The files are compiled with different scheduling
+// strategies (Makefile), never different arithmetic.
 #pragma once
 
 #include <type_traits>
@@ -69,54 +70,96 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void *row, int6
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(row), 0, (int)(uint32_t)bytes, 0x00020000);
 }
 
-// The rows of the three record planes a multi-record launch walks through (row r of a plane is
-// batch x 16 B for gd / am, batch x 8 B for my; the window wraps).  Rows are read through buffer
+// One aligned plane element of a row: 16 B is one load, a double4 two (the second at the
+// instruction's immediate offset).  AUX: the cache policy bits.
+template <int AUX>
+__device__ __forceinline__ void row_load(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t so, float4 &v) {
+    v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, so, AUX));
+}
+template <int AUX>
+__device__ __forceinline__ void row_load(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t so, float2 &v) {
+    v = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs, off, so, AUX));
+}
+template <int AUX>
+__device__ __forceinline__ void row_load(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t so, double2 &v) {
+    v = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, off, so, AUX));
+}
+template <int AUX>
+__device__ __forceinline__ void row_load(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t so, double4 &v) {
+    double2 lo, hi;
+    row_load<AUX>(rs, off, so, lo);
+    row_load<AUX>(rs, off + 16u, so, hi);
+    v = make_double4(lo.x, lo.y, hi.x, hi.y);
+}
+
+// The rows of the three record planes a multi-record launch walks through, for the 40 B record (R =
+// Rec: row r of a plane is batch x 16 B for gd / am, batch x 8 B for my) and the 80 B FP64 record
+// (Rec64: batch x 32 B and batch x 16 B); the window wraps.  Rows are read through buffer
 // descriptors of a CHUNK of consecutive rows with the row's offset inside the chunk in the
 // instruction's scalar offset (soffset), so moving to the next row is two scalar adds and a compare,
 // and the descriptors are rebuilt only when a chunk ends: chunk offsets stay below 2^31 (128 rows at
 // config 3, the whole 1,024-row window at config 2).  Each descriptor's record count is its chunk's
 // byte size and the range check covers soffset (measured: scripts/buffer_range_probe.hip), so an
-// offset past the chunk would read zeros, never another allocation.
+// offset past the chunk would read zeros, never another allocation.  The lane offsets are 32-bit:
+// batch < 2^28 (Rec) or 2^27 (Rec64), checked on the host.
+template <typename R>
 struct RowCursor {
+    using Big = decltype(R::gd);    // gd, am
+    using Small = decltype(R::my);
     const char *g, *a, *m;
-    uint32_t row16, row8;
+    uint32_t row_big, row_small;    // bytes per row
+    uint32_t off_big, off_small;    // this lane's offset within a row
     int32_t window, chunk_rows;
     int32_t row = 0, end = 0;
-    uint32_t s16 = 0, s8 = 0;
+    uint32_t s_big = 0, s_small = 0;
     __amdgpu_buffer_rsrc_t rg, ra, rm;
 
-    __device__ __forceinline__ RowCursor(const float4 *gd, const float4 *am, const float2 *my, int64_t batch,
-                                         int64_t win)
+    __device__ __forceinline__ RowCursor(const Big *gd, const Big *am, const Small *my, int64_t batch, int64_t win,
+                                         uint32_t lane)
         : g(reinterpret_cast<const char *>(gd)), a(reinterpret_cast<const char *>(am)),
-          m(reinterpret_cast<const char *>(my)), row16((uint32_t)batch * 16u), row8((uint32_t)batch * 8u),
-          window((int32_t)win) {
-        const uint32_t c = (1u << 31) / row16;
+          m(reinterpret_cast<const char *>(my)), row_big((uint32_t)batch * (uint32_t)sizeof(Big)),
+          row_small((uint32_t)batch * (uint32_t)sizeof(Small)), off_big(lane * (uint32_t)sizeof(Big)),
+          off_small(lane * (uint32_t)sizeof(Small)), window((int32_t)win) {
+        const uint32_t c = (1u << 31) / row_big;
         chunk_rows = c ? (int32_t)c : 1;
     }
     __device__ __forceinline__ void start(int32_t r) {
         row = r;
         end = (window - r < chunk_rows) ? window : r + chunk_rows;
         const uint64_t n = (uint64_t)(end - r);
-        rg = row_rsrc(g + (uint64_t)r * row16, (int64_t)(n * row16));
-        ra = row_rsrc(a + (uint64_t)r * row16, (int64_t)(n * row16));
-        rm = row_rsrc(m + (uint64_t)r * row8, (int64_t)(n * row8));
-        s16 = 0;
-        s8 = 0;
+        rg = row_rsrc(g + (uint64_t)r * row_big, (int64_t)(n * row_big));
+        ra = row_rsrc(a + (uint64_t)r * row_big, (int64_t)(n * row_big));
+        rm = row_rsrc(m + (uint64_t)r * row_small, (int64_t)(n * row_small));
+        s_big = 0;
+        s_small = 0;
     }
     __device__ __forceinline__ void advance() {
         if (++row == end) {
             start(row == window ? 0 : row);
         } else {
-            s16 += row16;
-            s8 += row8;
+            s_big += row_big;
+            s_small += row_small;
         }
     }
-    __device__ __forceinline__ Rec load(uint32_t off16, uint32_t off8) const {
-        Rec v;
-        v.gd = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rg, off16, s16, PEKF_REC_AUX));
-        v.am = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra, off16, s16, PEKF_REC_AUX));
-        v.my = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rm, off8, s8, PEKF_REC_AUX));
+    __device__ __forceinline__ R load() const {
+        R v;
+        row_load<PEKF_REC_AUX>(rg, off_big, s_big, v.gd);
+        row_load<PEKF_REC_AUX>(ra, off_big, s_big, v.am);
+        row_load<PEKF_REC_AUX>(rm, off_small, s_small, v.my);
         return v;
+    }
+    // acc / mag of the record `lag` rows behind the cursor again (rare: the degenerate-Wahba fallback),
+    // through one-row descriptors and the lane offsets the loop holds anyway (no 64-bit lane index is
+    // kept live for this)
+    __device__ __forceinline__ void reload(int32_t lag, double *acc, double *mag) const {
+        int32_t r = row - lag;
+        while (r < 0) r += window;
+        Big va;
+        Small vm;
+        row_load<0>(row_rsrc(a + (uint64_t)r * row_big, row_big), off_big, 0, va);
+        row_load<0>(row_rsrc(m + (uint64_t)r * row_small, row_small), off_small, 0, vm);
+        acc[0] = va.x; acc[1] = va.y; acc[2] = va.z;
+        mag[0] = va.w; mag[1] = vm.x; mag[2] = vm.y;
     }
 };
 
@@ -144,12 +187,6 @@ __device__ __forceinline__ double state_norm2(const double *x) {
     return fabs(n2 - 1.0) < 1e-13 ? 1.0 : n2;
 }
 
-// One record of main_file.py:42-45 -- Prediction(gyro, T) then Correction(mag, acc) -- on the
-// lane's state (x, P) in registers, in the world basis (Wf: the reference pair's Frame) or in the
-// reference frame's own basis (Wf: a RefW, see pekf_math.hpp); n2 = state_norm2 of x (1 for every record after a launch's
-// first).  gy = the gyro sample, dt_ns = T - previousT, missing: the record has no magnetometer
-// sample (Wahba-skip, X = z, P = P-).  Shared by the fused stream kernel and the handle's
-// per-record update, so both give bit-identical results for the same inputs.
 // a * b - c as one three-address v_fma_f64 with a negated operand.  Left to itself the compiler
 // picks the accumulating v_fmac_f64 for e = v sc - z and sets -z up in the accumulator registers
 // ahead of the rare Wahba fallback branch (a negation and two register copies per component).
@@ -185,17 +222,6 @@ __device__ __forceinline__ StepK<PT> step_consts(double qs, double rs) {
     return {(PT)(2.0 * g), (PT)(2.0 * rs), (PT)rs, (PT)(2.0 * (rs * rs)), 0.5 / rs};
 }
 
-// MC (the multi-record loop) also leaves X unnormalised, X = x / |x| with |x| ~ 0.7: its norm
-// folds into the next record's RK4 normalisation (z = rk4(x) / |rk4(x)| whatever |x|) and Jb term
-// (g (|X|^2 I - X X^T) = g I - (g / |x|^2) x x^T, |X|^2 = 1 as state_norm2 snaps it), and
-// 1/|x|^2 = in^2 kk comes from RK4's own rsqrt: 8 operations instead of the 13 of normalising X.
-// LAZY: x arrives that way (n2 ignored); the caller normalises once at the end of the launch.
-// OM (the FP64 multi-record loop, inside OmodMode): the exact halvings fold into the instructions
-// that form the products (omod, pekf_math.hpp) -- the gyro is never scaled to h = w/2, and the
-// Newton steps of the rsqrt seeds need no separate multiply by 1/2: 9 VALU fewer per record, the
-// same values bit for bit.
-// reload(acc, mag) re-reads the record's samples for the rare degenerate-Wahba fallback
-// (wahba_quat_toward); it is not called on the common path.
 // Wahba-skip: no Correction for this record (X = z, P = P- = S - rI)
 template <typename PT, bool MC>
 __device__ __forceinline__ void record_skip(double *x, const double *z, Sym4T<PT> &P, const Sym4T<PT> &S2,
@@ -243,12 +269,36 @@ __device__ __forceinline__ void record_correct(double *x, const double *z, Sym4T
     }
 }
 
+// One record of main_file.py:42-45 -- Prediction(gyro, T) then Correction(mag, acc) -- on the
+// lane's state (x, P) in registers, in the world basis (Wf: the reference pair's Frame) or in the
+// reference frame's own basis (Wf: a RefW / RefWLazy, pekf_math.hpp); n2 = state_norm2 of x (1 for
+// every record after a launch's first).  gy = the gyro sample, dt_ns = T - previousT, missing: the
+// record has no magnetometer sample (record_skip).  Shared by the fused stream kernels, k_live and
+// the handle's per-record update, so all give bit-identical results for the same inputs.
+// reload(acc, mag) re-reads the record's samples for the rare degenerate-Wahba fallback
+// (wahba_toward_from_product); it is not called on the common path.
+// MC (the multi-record loop): the covariance is carried as N (StepK), and X is left unnormalised,
+// X = x / |x| with |x| ~ 0.7: its norm folds into the next record's RK4 normalisation
+// (z = rk4(x) / |rk4(x)| whatever |x|) and Jb term (g (|X|^2 I - X X^T) = g I - (g / |x|^2) x x^T,
+// |X|^2 = 1 as state_norm2 snaps it), and 1/|x|^2 = in^2 kk comes from RK4's own rsqrt: 8 operations
+// instead of the 13 of normalising X.
+// LAZY: x arrives that way (n2 ignored); the caller normalises once at the end of the launch.
+// OM (the FP64 multi-record loop, inside OmodMode): the exact halvings fold into the instructions
+// that form the products (omod, pekf_math.hpp) -- the gyro is never scaled to h = w/2, and the
+// Newton steps of the rsqrt seeds need no separate multiply by 1/2: 9 VALU fewer per record, the
+// same values bit for bit.
+// PIN (with MC and OM): S^-1 depends only on the Prediction; it is held ahead of the rare fallback
+// branch, in the basic block of the Wahba chain, so that the two independent chains interleave (left
+// to itself the compiler sinks it past the branch, behind the Wahba chain).  Worth it where a SIMD
+// has one wave and the record's dependency chain is exposed (config 2: -2.3 %); neutral at 3 waves
+// per SIMD (config 3), where the other waves fill those gaps anyway (profiles/r2/ab_pin_schur/).
 // HOIST (the FP64 multi-record loop only): the Correction's state-independent half -- S^-1 and
 // Wahba's unnormalised quaternion q' -- is formed ahead of the missing-magnetometer branch, in the
 // Prediction's basic block (held there by an empty asm), so one block carries two independent
 // dependency chains (the Prediction's and the record's own); only q'.z, its scale and flip and the
 // update stay behind the branch.  For launches of at most one wave per SIMD (config 2), where nothing
-// else fills the chain's stalls (launch_run_multi selects it).  The same arithmetic, bit for bit.
+// else fills the chain's stalls (launch_run_multi selects it).
+// PIN and HOIST move instructions only: the arithmetic is the same, bit for bit.
 template <typename PT, bool MC = false, bool LAZY = false, bool OM = false, bool PIN = false, bool HOIST = false,
           typename Ref, typename Reload>
 __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> &P, const Ref &Wf, const StepK<PT> &k,
@@ -301,28 +351,12 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> 
         return;
     }
     if (missing) {
-        // Wahba-skip: no Correction for this record (X = z, P = P- = S - rI)
-        x[0] = z[0]; x[1] = z[1]; x[2] = z[2]; x[3] = z[3];
-        const PT hf = PT(0.5);
-        if (MC)  // D N D = (S - 2r I) / beta = S^/2 - rb I
-            P = {fma(hf, S2.a00, -k.r2), hf * S2.a01, -hf * S2.a02, -hf * S2.a03, fma(hf, S2.a11, -k.r2),
-                 -hf * S2.a12, -hf * S2.a13, fma(hf, S2.a22, -k.r2), hf * S2.a23, fma(hf, S2.a33, -k.r2)};
-        else
-            P = {fma(hf, S2.a00, -k.rp), hf * S2.a01, hf * S2.a02, hf * S2.a03, fma(hf, S2.a11, -k.rp),
-                 hf * S2.a12, hf * S2.a13, fma(hf, S2.a22, -k.rp), hf * S2.a23, fma(hf, S2.a33, -k.rp)};
+        record_skip<PT, MC>(x, z, P, S2, k);
     } else {
         // K = P- S^-1 = I - r S^-1  (:64-66); Si = S^-1 / 2, or (MC) the next N = -D (S^)^-1 D
         const Sym4T<PT> Si = spd_inverse_schur<PT, true, MC>(S2);
-
-        // ---- Correction (ExtendedKalmanFilter.py:70-80) ----
         const double ka = fabs(acc[2]);              // (:71)
         double v[4], sc;
-        // PIN: S^-1 depends only on the Prediction; have it computed before the rare fallback branch,
-        // in the basic block of the Wahba chain, so that the two independent chains interleave (left
-        // to itself the compiler sinks it past the branch, behind the Wahba chain).  Worth it where a
-        // SIMD has one wave and the record's dependency chain is exposed (config 2: -2.3 %); neutral at
-        // 3 waves per SIMD (config 3), where the other waves fill those gaps anyway
-        // (profiles/r2/ab_pin_schur/).  Scheduling only: the arithmetic is the same, bit for bit.
         auto pin = [&] {
             if constexpr (PIN && MC && OM)
                 asm volatile("" ::"v"(Si.a00), "v"(Si.a01), "v"(Si.a02), "v"(Si.a03), "v"(Si.a11), "v"(Si.a12),
@@ -337,39 +371,14 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> 
         } else {
             wahba_quat_toward<F>(Wf, acc, mag, ka, 1.0 - ka, z, v, sc, reload, pin);
         }
-        // e = Y - z (MC: D e, whose last two components are z - Y)
-        const PT e0 = (PT)fma_sub(v[0], sc, z[0]), e1 = (PT)fma_sub(v[1], sc, z[1]);
-        const PT e2 = (PT)(MC ? fma_rsub(v[2], sc, z[2]) : fma_sub(v[2], sc, z[2]));
-        const PT e3 = (PT)(MC ? fma_rsub(v[3], sc, z[3]) : fma_sub(v[3], sc, z[3]));
-        // X = z + K e = Y - r S^-1 e (:77), normalised (:79): X ~ Y / (2r) - S^-1 e / 2, or (MC,
-        // S^-1 = -(2/beta) D Si D) X ~ Y / sqrt(2) + D Si D e
-        const double u0 = Si.a00 * e0 + Si.a01 * e1 + Si.a02 * e2 + Si.a03 * e3;
-        const double u1 = Si.a01 * e0 + Si.a11 * e1 + Si.a12 * e2 + Si.a13 * e3;
-        const double u2 = Si.a02 * e0 + Si.a12 * e1 + Si.a22 * e2 + Si.a23 * e3;
-        const double u3 = Si.a03 * e0 + Si.a13 * e1 + Si.a23 * e2 + Si.a33 * e3;
-        const double sr = sc * k.sy;
-        const double x0 = fma(v[0], sr, MC ? u0 : -u0), x1 = fma(v[1], sr, MC ? u1 : -u1);
-        const double x2 = fma(v[2], sr, -u2), x3 = fma(v[3], sr, -u3);
-        if (MC) {
-            x[0] = x0; x[1] = x1; x[2] = x2; x[3] = x3;
-        } else {
-            const double in = rsqrt<true>(x0 * x0 + x1 * x1 + x2 * x2 + x3 * x3);
-            x[0] = x0 * in; x[1] = x1 * in; x[2] = x2 * in; x[3] = x3 * in;
-        }
-        // P = P- - K P- = r K = r I - r^2 S^-1 = r I - (2 r^2) Si (:78)
-        if (MC) {
-            P = Si;  // P = rI + beta D N D: nothing to compute
-        } else {
-            const PT rp = k.rp, rr = k.rr;
-            P = {rp - rr * Si.a00, -rr * Si.a01, -rr * Si.a02, -rr * Si.a03, rp - rr * Si.a11,
-                 -rr * Si.a12, -rr * Si.a13, rp - rr * Si.a22, -rr * Si.a23, rp - rr * Si.a33};
-        }
+        record_correct<PT, MC>(x, z, P, Si, v, sc, k);
     }
 }
 
-// A multi-record launch runs the filter in its reference frame's own basis (RefW in pekf_math.hpp)
-// with the covariance carried as N, P = rI + beta D N D (StepK).  to_ref_basis: the state entering
-// the launch, x -> q_W^* x, P -> N of q_W^* P q_W; from_ref_basis: back at its end, X normalised.
+// A multi-record launch runs the filter in its reference frame's own basis (RefW in pekf_math.hpp:
+// the same filter, with Wahba's rotation 24 operations cheaper per record) with the covariance
+// carried as N, P = rI + beta D N D (StepK); the state is rotated in once and out once per launch.
+// to_ref_basis: the state entering the launch, x -> q_W^* x, P -> N of q_W^* P q_W.
 template <typename PT>
 __device__ __forceinline__ void to_ref_basis(const double *qw, double *x, Sym4T<PT> &P, double rs) {
     double xw[4];
@@ -380,16 +389,44 @@ __device__ __forceinline__ void to_ref_basis(const double *qw, double *x, Sym4T<
     P = {(P.a00 - rp) * ib, P.a01 * ib, -P.a02 * ib, -P.a03 * ib, (P.a11 - rp) * ib,
          -P.a12 * ib, -P.a13 * ib, (P.a22 - rp) * ib, P.a23 * ib, (P.a33 - rp) * ib};
 }
+// The launch's prologue: the reference pair's Frame as the RefW (HOLD: q_W held through the loop, for
+// trajectory output) or the RefWLazy (q_W recomputed from `pair` at the launch's end and in the rare
+// fallback: 8 VGPRs fewer), and (x, P) into its basis.  idle (HOLD only): a filter with no records in
+// this launch rotates by the identity, which is exact; its state is not written back.
+template <bool HOLD, typename PT>
+__device__ __forceinline__ std::conditional_t<HOLD, RefW, RefWLazy> enter_ref_basis(const Frame &Wf, const double *pair,
+                                                                                    bool idle, double *x,
+                                                                                    Sym4T<PT> &P, double rs) {
+    std::conditional_t<HOLD, RefW, RefWLazy> Wr;
+    Wr.aW = Wf.alpha; Wr.b1W = Wf.beta1; Wr.b2W = Wf.beta2;
+    double qw[4];
+    frame_quat(Wf, qw);
+    if constexpr (HOLD) {
+        if (idle) { qw[0] = 1.0; qw[1] = qw[2] = qw[3] = 0.0; }
+        Wr.q[0] = qw[0]; Wr.q[1] = qw[1]; Wr.q[2] = qw[2]; Wr.q[3] = qw[3];
+    } else {
+        Wr.pair = pair;
+    }
+    to_ref_basis(qw, x, P, rs);
+    return Wr;
+}
+// The loop's unnormalised reference-basis X as the world-basis unit quaternion (a trajectory row,
+// the launch's final X); qw: q_W, as the caller may want it too
+template <typename RW>
+__device__ __forceinline__ void ref_to_world(const RW &Wr, const double *x, double *xo, double *qw) {
+    const double in = rsqrt<true>(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]);
+    const double xn[4] = {x[0] * in, x[1] * in, x[2] * in, x[3] * in};
+    Wr.quat(qw);
+    qmul_left<false>(qw, xn, xo);
+}
+// from_ref_basis: back at the launch's end, X normalised.
 template <typename PT, typename RW>
 __device__ __forceinline__ void from_ref_basis(const RW &Wr, double *x, Sym4T<PT> &P, double rs) {
     const PT be = (PT)(kSqrt2 * rs), rp = (PT)rs;
     P = {fma(be, P.a00, rp), be * P.a01, -be * P.a02, -be * P.a03, fma(be, P.a11, rp),
          -be * P.a12, -be * P.a13, fma(be, P.a22, rp), be * P.a23, fma(be, P.a33, rp)};
-    const double in = rsqrt<true>(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]);
-    const double xn[4] = {x[0] * in, x[1] * in, x[2] * in, x[3] * in};
     double xo[4], qw[4];
-    Wr.quat(qw);
-    qmul_left<false>(qw, xn, xo);
+    ref_to_world(Wr, x, xo, qw);
     x[0] = xo[0]; x[1] = xo[1]; x[2] = xo[2]; x[3] = xo[3];
     P = sym_rotate<false>(qw, P);
 }
@@ -404,92 +441,36 @@ __device__ __forceinline__ void from_ref_basis(const RW &Wr, double *x, Sym4T<PT
 #define PEKF_RUN_ATTR
 #endif
 
+// The multi-record stream kernel: n_steps >= 1 records of main_file.py:42-45 per filter, one lane per
+// filter, instantiated by pekf_run_multi.hip alone (one-record launches: k_run_one, pekf_run.hip).
+// R: the record in the planes -- Rec (40 B: f32 samples, a u32 dt word with the missing-magnetometer
+// bit) or Rec64 (80 B of doubles: dt the float64 T - previousT itself, any pause, clock step or
+// fraction, no escape word; every record carries a magnetometer sample, as a log's always does).
 // MIXED = false: every operation in FP64 (the headline path).
 // MIXED = true (opt-in, PEKF_RUN_MIXED_PRECISION): the covariance recursion (P-, S^-1, K, P)
 // in FP32 while RK4, Wahba, R->q and the X update stay FP64 (~2e-8 vs FP64).
 // COUNTS: filter b applies only its first counts[b] records of the launch (a separate
 // instantiation so the uniform-length path carries no per-step lane predicate).
 // PIN: the Schur-inverse-first schedule of the multi-record loop (ekf_record_step, launch_run_multi).
-// LONGDT: the window has a dt side plane dtx[window][batch] (float64 ns): a record whose dt word is
+// LONGDT (Rec): the window has a dt side plane dtx[window][batch] (float64 ns): a record whose dt word is
 // PEKF_DT_ESCAPE takes its dt from there -- gaps of 2^31 ns or more, negative or fractional ones, any
 // T - previousT the reference accepts (ExtendedKalmanFilter.py:62).  A separate instantiation, so the
 // windows without escapes (every synthetic and front-end stream but the rare long pause) pay nothing.
 // HOIST: the Correction's state-independent half ahead of the missing branch (ekf_record_step).
-template <bool TRAJ, bool MIXED, bool SOA, bool COUNTS, bool ONE, bool PIN = false, bool LONGDT = false,
+template <typename R, bool TRAJ, bool MIXED, bool SOA, bool COUNTS, bool PIN = false, bool LONGDT = false,
           bool HOIST = false>
 __global__ __launch_bounds__(kRunBlock) PEKF_RUN_ATTR void k_run(int64_t batch, int64_t n_steps, int64_t window,
-                                                   int64_t step0, const float4 *__restrict__ gd,
-                                                   const float4 *__restrict__ am,
-                                                   const float2 *__restrict__ my,
+                                                   int64_t step0, const decltype(R::gd) *__restrict__ gd,
+                                                   const decltype(R::gd) *__restrict__ am,
+                                                   const decltype(R::my) *__restrict__ my,
                                                    const double *__restrict__ refs,
                                                    double *__restrict__ Xio, double *__restrict__ Pio,
                                                    double qs, double rs, double *__restrict__ traj,
                                                    const int32_t *__restrict__ counts,
                                                    const double *__restrict__ dtx) {
     using PT = typename std::conditional<MIXED, float, double>::type;
-    if constexpr (ONE) {
-        // one-record launch (online serving): the state and the reference pair are most of the
-        // traffic.  The AoS state and the [batch][6] reference pairs move in coalesced wave tiles
-        // (pekf_tile.hpp) instead of 128 / 48 B-strided per-lane accesses; the SoA state is read and
-        // written per lane, one contiguous 512 B access per component and wave.
-        constexpr int kTile = SOA ? 6 : 16;
-        __shared__ double pool[kRunBlock / kWave * tile_doubles<kTile>()];
-        const WaveTile t(pool, tile_doubles<kTile>(), batch);
-        double cx[4], cp[16], cr[6];
-        if constexpr (!SOA) {
-            t.gather(Xio, cx);
-            t.gather(Pio, cp);
-        }
-        t.gather(refs, cr);
-        const bool act = t.active();
-        const uint32_t lane = act ? (uint32_t)(t.first + t.lane) : 0u;  // idle lanes read a valid row
-        const int64_t base = (step0 % window) * batch;
-        const Rec cur = {(gd + base)[lane], (am + base)[lane], (my + base)[lane]};
-        const bool run = act && (!COUNTS || counts[lane] > 0);
-        double x[4], pv[16], rf[6];
-        Sym4T<PT> P;
-        if constexpr (SOA) {
-            load_state<true>(Xio, Pio, lane, batch, x, P);
-        } else {
-            t.to_lanes(cx, x);
-            t.to_lanes(cp, pv);
-            P = sym_from16<PT>(pv);
-        }
-        t.to_lanes(cr, rf);
-        Frame Wf;
-        make_frame<true>(rf, rf + 3, Wf);
-        if (run) {
-            const double gy[3] = {cur.gd.x, cur.gd.y, cur.gd.z};
-            const uint32_t word = __float_as_uint(cur.gd.w);
-            const double acc[3] = {cur.am.x, cur.am.y, cur.am.z};
-            const double mag[3] = {cur.am.w, cur.my.x, cur.my.y};
-            double dtn = (double)(word & PEKF_DT_MASK);
-            if constexpr (LONGDT) {
-                if ((word & PEKF_DT_MASK) == PEKF_DT_ESCAPE) dtn = (dtx + base)[lane];
-            }
-            auto reload = [&](double *a, double *m) {  // rare: the degenerate-Wahba fallback
-                const float4 va = (am + base)[lane];
-                const float2 vm = (my + base)[lane];
-                a[0] = va.x; a[1] = va.y; a[2] = va.z;
-                m[0] = va.w; m[1] = vm.x; m[2] = vm.y;
-            };
-            ekf_record_step<PT>(x, state_norm2(x), P, Wf, step_consts<PT, false>(qs, rs), gy, dtn,
-                                (word & PEKF_MISSING_MAG_BIT) != 0, acc, mag, reload);
-        }
-        if (TRAJ && act) {
-            double2 *o = reinterpret_cast<double2 *>(traj) + 2 * (int64_t)lane;
-            o[0] = make_double2(x[0], x[1]);
-            o[1] = make_double2(x[2], x[3]);
-        }
-        if constexpr (SOA) {
-            if (act) store_state<true>(Xio, Pio, lane, batch, x, P);
-        } else {
-            sym_to16(P, pv);
-            t.store(Xio, x);
-            t.store(Pio, pv);
-        }
-        return;
-    }
+    constexpr bool kRec64 = std::is_same<R, Rec64>::value;
+    static_assert(!(kRec64 && LONGDT), "an FP64 record's dt is the float64 itself: no side plane");
     const int64_t b = (int64_t)blockIdx.x * kRunBlock + threadIdx.x;
     if (b >= batch) return;
     const int32_t my_steps = COUNTS ? (counts[b] < n_steps ? counts[b] : (int32_t)n_steps) : (int32_t)n_steps;
@@ -507,57 +488,45 @@ __global__ __launch_bounds__(kRunBlock) PEKF_RUN_ATTR void k_run(int64_t batch, 
 
     // Record of stream row r: raw buffer loads whose lane offset is fixed and whose row offset is
     // the wave-uniform soffset within a chunk of rows (RowCursor), so a record costs two scalar adds
-    // and a compare of address work, no per-step vector address arithmetic (batch < 2^28 is checked
-    // on the host, so the offsets fit).
+    // and a compare of address work, no per-step vector address arithmetic.
     const uint32_t lane = (uint32_t)b;
-    const uint32_t off16 = lane * 16u, off8 = lane * 8u;
-    RowCursor rows(gd, am, my, batch, window);
+    RowCursor<R> rows(gd, am, my, batch, window, lane);
     // rows the cursor runs ahead of the record a step works on (ping-pong: one; deeper prefetch rings
     // were measured and not kept, profiles/r1/README.md)
     constexpr int32_t kLag = 1;
-    // One record: Prediction + Correction (main_file.py:42-45) on (x, P) in registers.
-    auto step = [&](const Rec &cur, int32_t t, double n2, const auto &ref, auto lazy) {
-        // the multi-record loop (RefW) carries N and an unnormalised X, the one-record launch
-        // (Frame) P and X; lazy: X arrives unnormalised (every multi-record step after the first)
-        constexpr bool MC = !std::is_same<std::decay_t<decltype(ref)>, Frame>::value;
+    rows.start((int32_t)(step0 % window));
+    R ra = rows.load(), rb;
+    // Without trajectory output q_W is recomputed where it is needed rather than held through the loop
+    const auto Wr = enter_ref_basis<TRAJ>(Wf, refs + 6 * b, COUNTS && my_steps == 0, x, P, rs);
+    // One record: Prediction + Correction (main_file.py:42-45) on (x, P) in registers, in the
+    // reference basis with the covariance as N; lazy: X arrives unnormalised (every record after the
+    // launch's first)
+    auto step = [&](const R &cur, int32_t t, double n2, auto lazy) {
         if (!COUNTS || t < my_steps) {
             const double gy[3] = {cur.gd.x, cur.gd.y, cur.gd.z};
-            const uint32_t word = __float_as_uint(cur.gd.w);
             const double acc[3] = {cur.am.x, cur.am.y, cur.am.z};
             const double mag[3] = {cur.am.w, cur.my.x, cur.my.y};
-            double dtn = (double)(word & PEKF_DT_MASK);
-            if constexpr (LONGDT) {  // the escaped record's row, (step0 + t) % window (rare: off the fast path)
-                if ((word & PEKF_DT_MASK) == PEKF_DT_ESCAPE) dtn = dtx[((step0 + t) % window) * batch + b];
+            double dtn;
+            bool missing = false;
+            if constexpr (kRec64) {
+                dtn = cur.gd.w;
+            } else {
+                const uint32_t word = __float_as_uint(cur.gd.w);
+                dtn = (double)(word & PEKF_DT_MASK);
+                if constexpr (LONGDT) {  // the escaped record's row, (step0 + t) % window (rare: off the fast path)
+                    if ((word & PEKF_DT_MASK) == PEKF_DT_ESCAPE) dtn = dtx[((step0 + t) % window) * batch + b];
+                }
+                missing = (word & PEKF_MISSING_MAG_BIT) != 0;
             }
-            auto reload = [&](double *a, double *m) {  // rare: this record again; the cursor is kLag rows ahead
-                int32_t r = rows.row - kLag;
-                while (r < 0) r += rows.window;
-                // through one-row descriptors and the lane offsets the loop holds anyway (no 64-bit
-                // lane index is kept live for this)
-                const float4 va = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                    row_rsrc(rows.a + (uint64_t)r * rows.row16, rows.row16), off16, 0, 0));
-                const float2 vm = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(
-                    row_rsrc(rows.m + (uint64_t)r * rows.row8, rows.row8), off8, 0, 0));
-                a[0] = va.x; a[1] = va.y; a[2] = va.z;
-                m[0] = va.w; m[1] = vm.x; m[2] = vm.y;
-            };
-            ekf_record_step<PT, MC, decltype(lazy)::value, MC && !MIXED, PIN, HOIST && MC && !MIXED>(
-                x, n2, P, ref, step_consts<PT, MC>(qs, rs), gy, dtn, (word & PEKF_MISSING_MAG_BIT) != 0, acc, mag,
-                reload);
+            auto reload = [&](double *a, double *m) { rows.reload(kLag, a, m); };  // rare: this record again
+            ekf_record_step<PT, true, decltype(lazy)::value, !MIXED, PIN, HOIST && !MIXED>(
+                x, n2, P, Wr, step_consts<PT, true>(qs, rs), gy, dtn, missing, acc, mag, reload);
         }
         if (TRAJ) {
-            double xo[4] = {x[0], x[1], x[2], x[3]};
             // a filter with no records in this launch (COUNTS) repeats its stored X unchanged
             // (x was rotated by the identity, which is exact; it is not normalised or written back)
-            if constexpr (MC) {
-                if (!COUNTS || my_steps > 0) {
-                    const double in = rsqrt<true>(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]);
-                    const double xn[4] = {x[0] * in, x[1] * in, x[2] * in, x[3] * in};
-                    double qw[4];
-                    ref.quat(qw);
-                    qmul_left<false>(qw, xn, xo);
-                }
-            }
+            double xo[4] = {x[0], x[1], x[2], x[3]}, qw[4];
+            if (!COUNTS || my_steps > 0) ref_to_world(Wr, x, xo, qw);
             double2 *o = reinterpret_cast<double2 *>(traj + (int64_t)t * batch * 4) + 2 * (int64_t)lane;
             o[0] = make_double2(xo[0], xo[1]);
             o[1] = make_double2(xo[2], xo[3]);
@@ -569,49 +538,24 @@ __global__ __launch_bounds__(kRunBlock) PEKF_RUN_ATTR void k_run(int64_t batch, 
     // Time loop, unrolled by two with ping-pong records: the next row's record is always in
     // flight while the current one is processed, and no registers are copied between steps.
     // The prefetch is unconditional (the row wraps inside the resident window, so it is always
-    // a valid address); n_steps >= 1 here.  One-record launches (online serving) use the ONE
-    // instantiation, which has no prefetch: there its 40 B would be an eighth of the traffic.
-    rows.start((int32_t)(step0 % window));
-    Rec ra = rows.load(off16, off8), rb;
-    // A multi-record launch runs the filter in its reference frame's own basis (RefW in
-    // pekf_math.hpp: the same filter, with Wahba's rotation 24 operations cheaper per record);
-    // the state is rotated in once and out once per launch.  A filter with no records in this
-    // launch (COUNTS) rotates by the identity, which is exact, and its state is not written back.
-    // Inside the loop the covariance is carried as N, P = rI + beta D N D (StepK).
-    // Without trajectory output q_W is recomputed at the launch's end (and in the rare fallback)
-    // rather than held through the loop (RefWLazy: 8 VGPRs).
-    using RW = typename std::conditional<TRAJ, RefW, RefWLazy>::type;
-    RW Wr;
-    Wr.aW = Wf.alpha; Wr.b1W = Wf.beta1; Wr.b2W = Wf.beta2;
-    {
-        double qw[4];
-        frame_quat(Wf, qw);
-        if constexpr (TRAJ) {
-            if (COUNTS && my_steps == 0) { qw[0] = 1.0; qw[1] = qw[2] = qw[3] = 0.0; }
-            Wr.q[0] = qw[0]; Wr.q[1] = qw[1]; Wr.q[2] = qw[2]; Wr.q[3] = qw[3];
-        } else {
-            Wr.pair = refs + 6 * b;
-        }
-        to_ref_basis(qw, x, P, rs);
-    }
-    // The launch's first record takes |X|^2 from the loaded state; from then on the state is
-    // unit and n2 = 1 is a compile-time constant (see state_norm2).  32-bit step counter
+    // a valid address).  The launch's first record takes |X|^2 from the loaded state; from then on
+    // the state is unit and n2 = 1 is a compile-time constant (see state_norm2).  32-bit step counter
     // (n_steps < 2^31 is checked on the host).
     const int32_t n32 = (int32_t)n_steps;
     rows.advance();
-    rb = rows.load(off16, off8);
+    rb = rows.load();
     // the FP64 loop folds its exact halvings into output modifiers, which need this MODE
     OmodMode mode;
     if constexpr (!MIXED) mode.enter();
-    step(ra, 0, state_norm2(x), Wr, eager{});
+    step(ra, 0, state_norm2(x), eager{});
     for (int32_t t = 1; t < n32;) {
         rows.advance();
-        ra = rows.load(off16, off8);
-        step(rb, t, 1.0, Wr, lazy{});
+        ra = rows.load();
+        step(rb, t, 1.0, lazy{});
         if (++t == n32) break;
         rows.advance();
-        rb = rows.load(off16, off8);
-        step(ra, t, 1.0, Wr, lazy{});
+        rb = rows.load();
+        step(ra, t, 1.0, lazy{});
         ++t;
     }
     if constexpr (!MIXED) mode.leave();
@@ -619,6 +563,5 @@ __global__ __launch_bounds__(kRunBlock) PEKF_RUN_ATTR void k_run(int64_t batch, 
     from_ref_basis(Wr, x, P, rs);
     store_state<SOA>(Xio, Pio, b, batch, x, P);
 }
-
 
 }  // namespace pekf

@@ -7,7 +7,7 @@ lines).  One JSON object on stdout; kernel times are HIP events on the launch st
   live_ev64      k_live, FP64 events (the server's stod values), all-FP64 records
   frontend_f32   k_frontend, f32 events -> 40 B records
   frontend_ev64  k_frontend, FP64 events -> 80 B FP64 records
-  run64_after    k_run64 over frontend_ev64's records (the FP64 split pipeline's second half)
+  run64_after    pekf_run_rec64_dev over frontend_ev64's records (the FP64 split pipeline's second half)
   init_f32 / init_ev64   k_frontend_init, means only
 
 PEKF_LIB selects the library (A/B of build variants); PEKF_EV64_ONLY=live skips the split pipeline."""

@@ -2,7 +2,8 @@
 fma_half & co.) only take effect inside the MODE window OmodMode opens (IEEE off, FP64 denormals
 flushed); outside it the hardware silently ignores the modifier and the result is off by 2x.  The
 inline asm of those helpers is ordered only by its data dependences, so this checks the emitted gfx950
-listing of every kernel that uses them (the multi-record k_run variants and k_live): each omod
+listing of every kernel that uses them (the multi-record k_run variants, over 40 B and FP64 records,
+and k_live): each omod
 instruction lies between the window's MODE write and the write that restores the saved MODE, in the
 same function.  CPU only (hipcc cross-compiles); ADVICE r2."""
 import os
@@ -121,7 +122,9 @@ def _check(lines):
 def test_omod_only_inside_the_mode_window_multi_record(tmp_path):
     lines = _listing("pekf_run_multi.hip", ["-mllvm", "--amdgpu-sched-strategy=max-ilp"], tmp_path)
     n_fn, n_omod = _check(lines)
-    assert n_fn >= 8 and n_omod > 1000      # every FP64 multi-record variant carries them
+    # every FP64 multi-record variant carries them: k_run<Rec, TRAJ, false, SOA, COUNTS, false, LONGDT> (16),
+    # its PIN and PIN + HOIST forms x SOA (4) and k_run<Rec64, TRAJ, .., COUNTS, ..> (4)
+    assert n_fn >= 24 and n_omod > 1000
 
 
 def test_omod_only_inside_the_mode_window_live(tmp_path):

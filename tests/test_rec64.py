@@ -5,7 +5,8 @@ that are float64 to begin with -- recorded logs, which the reference parses into
 * f32-representable values: bit for bit the 40 B-record launch (pekf_run_dev), the same step arithmetic;
 * config 1's log (natively parsed, float64) against the reference's own X_k (main_file.py:38-47);
 * float64 records with odd time differences against the NumPy restatement (oracle/ekf_numpy.py);
-* ragged logs in one launch (per-filter counts), each against its own reference run."""
+* ragged logs in one launch (per-filter counts), each against its own reference run;
+* launches of 1, 2 and 3 records (the prefetching loop's head: there is no one-record kernel here)."""
 import gzip
 import os
 
@@ -86,6 +87,60 @@ def test_rec64_float64_records_and_odd_dts_vs_numpy(eng):
         worst = max(worst, float(np.abs(tr[:, k] - want).max()))
     print("FP64 records with odd dts vs the NumPy restatement: max |dq| = %.3e" % worst)
     assert worst < ATOL_F64
+
+
+@pytest.fixture(scope="module")
+def short_case():
+    """65 filters (one full wave and one lane) on a 4-row window read from row 3, so the launch's first
+    prefetch wraps; per filter the NumPy restatement's (X, P) after 0..3 of its records."""
+    K, W, step0 = 65, 4, 3
+    rng = np.random.default_rng(65)
+    g = rng.normal(scale=0.5, size=(W, K, 3))
+    a = rng.normal(scale=0.3, size=(W, K, 3)) + [0.0, 0.0, 9.8]
+    m = rng.normal(scale=2.0, size=(W, K, 3)) + [20.0, 1.0, -40.0]
+    dt = rng.choice([1.0e7, 2.5e7 + 0.25, 3.2e9, -4.0e6], size=(W, K))
+    a0 = rng.normal(scale=0.3, size=(K, 3)) + [0.0, 0.0, 9.8]
+    m0 = rng.normal(scale=2.0, size=(K, 3)) + [20.0, 1.0, -40.0]
+    X0 = np.array([1.0, 0.0, 0.0, 0.0]) + rng.normal(scale=0.1, size=(K, 4))
+    X0 /= np.linalg.norm(X0, axis=1, keepdims=True)
+    A = rng.normal(scale=0.1, size=(K, 4, 4))
+    P0 = 0.5 * np.identity(4) + A @ A.transpose(0, 2, 1)
+    rows = (step0 + np.arange(3)) % W
+    after = [[(X0[k], P0[k])] + [npo.run_filter(g[rows[:n], k], dt[rows[:n], k], a[rows[:n], k], m[rows[:n], k],
+                                                 a0[k], m0[k], X0=X0[k], P0=P0[k], record=False)[:2]
+                                  for n in (1, 2, 3)] for k in range(K)]
+    counts = np.array([0, 1, 5, 2, 3] * 13, dtype=np.int32)   # 0, 1 and more than any n_steps below
+    return dict(K=K, step0=step0, arrays=(g, dt, a, m, a0, m0), X0=X0, P0=P0, after=after, counts=counts)
+
+
+@pytest.mark.parametrize("want_traj", [False, True])
+@pytest.mark.parametrize("n_steps", [1, 2, 3])
+def test_rec64_short_launches_vs_numpy(eng, short_case, n_steps, want_traj):
+    """Launches of 1, 2 and 3 records: the FP64-record entry has no one-record kernel, so these run the
+    prefetching loop's head and its early exits.  Per-filter counts of 0, 1 and more than n_steps: each
+    filter matches the NumPy restatement after its own records, and one with no record keeps its stored
+    state bit for bit (its trajectory rows repeat the stored X)."""
+    c = short_case
+    K, counts = c["K"], c["counts"]
+    f = eng.BatchedEKF(K)
+    f.set_state(c["X0"], c["P0"])
+    tr = f.run(eng.RecordWindow64.from_arrays(*c["arrays"]), n_steps=n_steps, step0=c["step0"],
+               want_traj=want_traj, counts=counts)
+    X, P = f.get_state()
+    applied = np.minimum(counts, n_steps)
+    idle = applied == 0
+    assert np.array_equal(X[idle], c["X0"][idle]) and np.array_equal(P[idle], c["P0"][idle])
+    ex = max(float(np.abs(X[k] - c["after"][k][applied[k]][0]).max()) for k in range(K))
+    ep = max(float(np.abs(P[k] - c["after"][k][applied[k]][1]).max()) for k in range(K))
+    print("FP64 records, %d-record launch: max |dX| = %.3e, max |dP| = %.3e" % (n_steps, ex, ep))
+    assert ex < ATOL_F64 and ep < ATOL_F64
+    if want_traj:
+        assert tr.shape == (n_steps, K, 4)
+        assert all(np.array_equal(tr[t, idle], c["X0"][idle]) for t in range(n_steps))
+        et = max(float(np.abs(tr[t, k] - c["after"][k][min(t + 1, applied[k])][0]).max())
+                 for t in range(n_steps) for k in range(K) if not idle[k])
+        print("  trajectory rows: max |dq| = %.3e" % et)
+        assert et < ATOL_F64
 
 
 def test_rec64_ragged_logs_in_one_launch(eng, tmp_path):
