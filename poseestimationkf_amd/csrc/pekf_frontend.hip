@@ -195,45 +195,23 @@ __global__ __launch_bounds__(64) void k_frontend(int64_t batch, int64_t n_events
         }
     };
 
-    // Events stream through a register ring of kRing records loaded kRing events ahead (the loop is
-    // unrolled by kRing so every ring index is static; the row is clamped to the last event, so the
-    // loads past the end read a valid row and need no predicate).  32-bit event counters (n_events <
-    // 2^30, checked on the host) keep the uniform tests scalar, and the last block is padded with null
-    // events (a zero-step time event moves no state) so no exit sits inside the unrolled body; nothing
-    // is pending after a whole block.
-    const uint32_t lane = (uint32_t)b;
-    const int32_t n_ev = (int32_t)n_events;
-    auto load = [&](int32_t e) -> EvT {
-        const int32_t row = e < n_ev ? e : n_ev - 1;
-        return load_event<PEKF_FE_NTL>(ev + (int64_t)row * batch + lane);
-    };
-    if (n_ev > 0) {
-        constexpr int kRing = EV64 ? PEKF_FE_RING64 : PEKF_FE_RING;  // events in flight per lane (a multiple of kFlush)
-        static_assert(kRing % kFlush == 0, "the ring depth must be a multiple of the flush period");
-        EvT ring[kRing];
-#pragma unroll
-        for (int k = 0; k < kRing; ++k) ring[k] = load(k);
-        for (int32_t e0 = 0; e0 < n_ev; e0 += kRing) {
-            if (e0 + kRing > n_ev) {  // uniform, once per launch
-#pragma unroll
-                for (int k = 0; k < kRing; ++k)
-                    if (e0 + k >= n_ev) ring[k] = null_event<EvT>();
+    // The events come through the load-ahead ring (pekf_phase3.hpp: event_ring); nothing is pending after
+    // a whole block.
+    constexpr int kRing = EV64 ? PEKF_FE_RING64 : PEKF_FE_RING;  // events in flight per lane (a multiple of kFlush)
+    static_assert(kRing % kFlush == 0, "the ring depth must be a multiple of the flush period");
+    event_ring<kRing, PEKF_FE_NTL>(
+        ev, batch, (uint32_t)b, (int32_t)n_events,
+        [&](int k, const EvT &v4) {
+            if constexpr (EV64)
+                fe.event64(v4);
+            else
+                fe.template event<TE>(v4);
+            if ((k + 1) % kFlush == 0) {
+                flush_pool();
+                drain_pool(false);
             }
-#pragma unroll
-            for (int k = 0; k < kRing; ++k) {
-                const EvT v4 = ring[k];
-                ring[k] = load(e0 + k + kRing);
-                if constexpr (EV64)
-                    fe.event64(v4);
-                else
-                    fe.template event<TE>(v4);
-                if ((k + 1) % kFlush == 0) {
-                    flush_pool();
-                    drain_pool(false);
-                }
-            }
-        }
-    }
+        },
+        [](bool) {});
     drain_pool(true);
     counts[b] = r < rmax ? r : rmax;
     if (bad && err) atomicOr(err, bad);
@@ -268,45 +246,26 @@ __global__ __launch_bounds__(kFeBlock) void k_frontend_init(int64_t batch, int64
     bool done[3] = {false, false, false};  // Acc_ / Gyr_ / Mag_initialized
     bool kalman = false;
     int64_t t = t_start[b], t_last = t;
-    // events come kInitRing rows at a time, all loads issued before the first is used (the loop body
-    // is a few adds, so without it each wave would wait out one memory latency per event).  32-bit
-    // event counters (n_events < 2^30, checked on the host) keep the uniform bounds tests scalar; the
-    // rows past the end of the last block are null events (a zero-step time event, which phase 2 skips
-    // in both passes), so no exit sits inside the unrolled body.
+    // events come kInitRing rows at a time (pekf_phase3.hpp: load_event_block); the null events that pad
+    // the last block are skipped by both passes
     constexpr int kInitRing = 8;
     const int32_t n_ev = (int32_t)n_events;
-    const EvT null_ev = null_event<EvT>();
-    auto row = [&](int32_t e) -> EvT {
-        return load_event<PEKF_INIT_NTL>(ev + (int64_t)(e < n_ev ? e : n_ev - 1) * batch + lane);
-    };
-    auto pad = [&](int32_t e0, EvT (&r)[kInitRing]) {
-        if (e0 + kInitRing > n_ev) {  // uniform: the last block only
-#pragma unroll
-            for (int k = 0; k < kInitRing; ++k)
-                if (e0 + k >= n_ev) r[k] = null_ev;
-        }
-    };
     for (int32_t e0 = 0; e0 < n_ev; e0 += kInitRing) {
         EvT r[kInitRing];
-#pragma unroll
-        for (int k = 0; k < kInitRing; ++k) r[k] = row(e0 + k);
-        pad(e0, r);
+        load_event_block<kInitRing, PEKF_INIT_NTL>(ev, batch, lane, e0, n_ev, r);
 #pragma unroll
         for (int k = 0; k < kInitRing; ++k) {
             const EvT v4 = r[k];
-            int ty;
+            const int ty = (int)event_type(v4);
             if constexpr (EV64) {
-                if (ev64_none(v4)) continue;  // no message
-                ty = (int)ev64_type(v4);
+                if (!is_message(v4)) continue;
                 t = (int64_t)ev64_time(v4);
             } else {
-                const uint32_t word = __float_as_uint(v4.w);
-                ty = (int)(word & 3u);
-                if (word == PEKF_EV_TIME) {  // a time event: the clock moves, nothing else happens
+                if (!is_message(v4)) {  // a time event: the clock moves, nothing else happens
                     t += (int64_t)time_step(v4);
                     continue;
                 }
-                t += (int64_t)(word >> 2);
+                t += (int64_t)(__float_as_uint(v4.w) >> 2);
             }
             if (!(done[0] && done[1] && done[2])) {
                 if (ty <= 2) {
@@ -338,17 +297,11 @@ __global__ __launch_bounds__(kFeBlock) void k_frontend_init(int64_t batch, int64
         // done once every type has its n_avg; a filter that never got ready reports NaN, so reads none
         if (!kalman || (c2[0] >= n_avg && c2[1] >= n_avg && c2[2] >= n_avg)) break;
         EvT r[kInitRing];
-#pragma unroll
-        for (int k = 0; k < kInitRing; ++k) r[k] = row(e0 + k);
-        pad(e0, r);
+        load_event_block<kInitRing, PEKF_INIT_NTL>(ev, batch, lane, e0, n_ev, r);
 #pragma unroll
         for (int k = 0; k < kInitRing; ++k) {
             const EvT v4 = r[k];
-            int ty;
-            if constexpr (EV64)
-                ty = (int)ev64_type(v4);
-            else
-                ty = (int)(__float_as_uint(v4.w) & 3u);
+            const int ty = (int)event_type(v4);
             if (ty <= 2 && c2[ty] < n_avg) {
 #pragma clang fp contract(off)
                 const double d0 = (double)v4.x - mean[ty][0], d1 = (double)v4.y - mean[ty][1],

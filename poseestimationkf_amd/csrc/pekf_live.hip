@@ -308,12 +308,6 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
             if (ready) queue.push(rc, esc, q.dt);
         }
     };
-    auto on_event = [&](const EvT &v4) {
-        if constexpr (EV64)
-            fe.event64(v4);
-        else
-            fe.template event<TE>(v4);
-    };
     auto flush = [&]() {
         if (fe.pend) {
             fe.pend = false;
@@ -321,29 +315,6 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
         }
     };
 
-    // Events stream through a register ring of kRing rows loaded kRing events ahead (the loop is
-    // unrolled by kRing so every ring index is static; rows past the end are clamped to the last one).
-    // 32-bit event counters (n_events < 2^30, checked on the host): the wave-uniform bounds tests are
-    // then scalar compares, where 64-bit ones took a VALU move and compare each, twice per event.
-    const uint32_t lane = (uint32_t)b;
-    const int32_t n_ev = (int32_t)n_events;
-    auto load = [&](int32_t e) -> EvT {
-        const int32_t row = e < n_ev ? e : n_ev - 1;
-#if PEKF_LIVE_NTL
-        if constexpr (EV64) {
-            typedef double nd2 __attribute__((ext_vector_type(2)));
-            const nd2 *q = (const nd2 *)(ev + (int64_t)row * batch + lane);
-            const nd2 lo = __builtin_nontemporal_load(q), hi = __builtin_nontemporal_load(q + 1);
-            return make_double4(lo.x, lo.y, hi.x, hi.y);
-        } else {
-            typedef float nv4 __attribute__((ext_vector_type(4)));
-            const nv4 v = __builtin_nontemporal_load((const nv4 *)(ev + (int64_t)row * batch + lane));
-            return make_float4(v.x, v.y, v.z, v.w);
-        }
-#else
-        return (ev + (int64_t)row * batch)[lane];
-#endif
-    };
     // wave-uniform: a step while some lane could overflow in the next block, then one more if a quorum
     // of lanes has a record; after the last event until every queue is empty; (R64) while some lane
     // still has an escaped record queued, so the next block cannot queue a second one on that lane
@@ -360,35 +331,18 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
             } while (want_step(last));
         }
     };
-    if (n_ev > 0) {
-        EvT ring[kRing];
-#pragma unroll
-        for (int k = 0; k < kRing; ++k) ring[k] = load(k);
-        // No exit inside the unrolled body (one per event made the compiler copy the ring on the back
-        // edge, behind a wait for the loads just issued): the last, partial block is padded with null
-        // events -- a zero-step time event {0, 0, 0, word 3} moves no state, with or without TE -- so
-        // every block runs whole, and nothing is pending after a whole block.
-        for (int32_t e0 = 0; e0 < n_ev; e0 += kRing) {
-            if (e0 + kRing > n_ev) {  // uniform, once per launch
-#pragma unroll
-                for (int k = 0; k < kRing; ++k)
-                    if (e0 + k >= n_ev) {
-                        if constexpr (EV64)
-                            ring[k] = ev64_null();
-                        else
-                            ring[k] = make_float4(0.f, 0.f, 0.f, __uint_as_float(PEKF_EV_TIME));
-                    }
-            }
-#pragma unroll
-            for (int k = 0; k < kRing; ++k) {
-                const EvT v4 = ring[k];
-                ring[k] = load(e0 + k + kRing);
-                on_event(v4);
-                if ((k + 1) % kFlush == 0) flush();
-            }
-            steps(e0 + kRing >= n_ev);
-        }
-    }
+    // The events come through the load-ahead ring (pekf_phase3.hpp: event_ring; its null events move no
+    // state, with or without TE); nothing is pending after a whole block, and a filter step may follow it.
+    event_ring<kRing, PEKF_LIVE_NTL>(
+        ev, batch, (uint32_t)b, (int32_t)n_events,
+        [&](int k, const EvT &v4) {
+            if constexpr (EV64)
+                fe.event64(v4);
+            else
+                fe.template event<TE>(v4);
+            if ((k + 1) % kFlush == 0) flush();
+        },
+        steps);
     counts[b] = applied;
     if (applied == 0) return;  // no record: the state is left as it was (as pekf_run_dev with counts)
     from_ref_basis(Wr, x, P, rs);

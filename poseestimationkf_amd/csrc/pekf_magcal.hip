@@ -12,8 +12,8 @@
 // called at KFS/Parser.cpp:107 (phase 2, the raw sample) and :239 (phase 3, the interpolated sample).
 //
 // k_magcal: two passes over the event planes of phase 2 / 3's form ([n_events][batch], float4 or, with
-// PEKF_EV_F64_EVENTS, double4), as k_frontend_init reads them (pekf_frontend.hip: the event ring, the
-// padding of the last block, scalar bounds).  Pass 1: the FP64 sum of the first n_cal samples in arrival
+// PEKF_EV_F64_EVENTS, double4), read with k_frontend_init's block reader (pekf_phase3.hpp:
+// load_event_block).  Pass 1: the FP64 sum of the first n_cal samples in arrival
 // order, divided by n_cal -- the reference's own sequence of operations, so the bias is its bias bit for
 // bit.  Pass 2: the 21 unique entries of A^T A and the 6 of A^T 1, summed in FP64 from zero (what
 // KFS/Matrix_multiplication.cu's ATA / ATb mean; that kernel adds into memory it never clears).  Then,
@@ -43,10 +43,6 @@ constexpr int kApplyRows = 64;     // k_magcal_apply: rows per lane at least (it
 // events (scripts/bench_magcal.py, interleaved twice): 12.0 ms; 8 rows in flight 12.1; whole 32 B events stored
 // 12.1; non-temporal loads 17.2 (the stores go to the lines just read).
 constexpr int kApplyRing = 4;
-
-// whether an event is a message of the phone (not a time event / not the no-message event)
-__device__ __forceinline__ bool is_message(const float4 &e) { return __float_as_uint(e.w) != PEKF_EV_TIME; }
-__device__ __forceinline__ bool is_message(const double4 &e) { return !ev64_none(e); }
 
 // index of entry (i, j), i <= j, of a symmetric 6 x 6 held as its 21 upper entries
 __host__ __device__ constexpr int sym6(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
@@ -85,17 +81,6 @@ __global__ __launch_bounds__(kMcBlock) void k_magcal(int64_t batch, int64_t n_ev
     if (b >= batch) return;
     const uint32_t lane = (uint32_t)b;
     const int32_t n_ev = (int32_t)n_events;  // < 2^30, checked on the host: the uniform tests stay scalar
-    const EvT null_ev = null_event<EvT>();   // not a message in either form
-    auto row = [&](int32_t e) -> EvT {
-        return load_event<kMcNtl>(ev + (int64_t)(e < n_ev ? e : n_ev - 1) * batch + lane);
-    };
-    auto pad = [&](int32_t e0, EvT (&r)[kMcRing]) {
-        if (e0 + kMcRing > n_ev) {  // uniform: the last block only
-#pragma unroll
-            for (int k = 0; k < kMcRing; ++k)
-                if (e0 + k >= n_ev) r[k] = null_ev;
-        }
-    };
     // pass 1: the sum of the first n_cal samples (setValues, :27-35); the lane counts its messages up to
     // n_cal + 1, the one that fires the fit (:18-25)
     double sx = 0.0, sy = 0.0, sz = 0.0;
@@ -103,9 +88,7 @@ __global__ __launch_bounds__(kMcBlock) void k_magcal(int64_t batch, int64_t n_ev
     for (int32_t e0 = 0; e0 < n_ev; e0 += kMcRing) {
         if (__all(cnt > n_cal)) break;  // every lane of the wave has seen its message n_cal + 1
         EvT r[kMcRing];
-#pragma unroll
-        for (int k = 0; k < kMcRing; ++k) r[k] = row(e0 + k);
-        pad(e0, r);
+        load_event_block<kMcRing, kMcNtl>(ev, batch, lane, e0, n_ev, r);  // padded with null events: no messages
 #pragma unroll
         for (int k = 0; k < kMcRing; ++k) {
 #pragma clang fp contract(off)
@@ -128,9 +111,7 @@ __global__ __launch_bounds__(kMcBlock) void k_magcal(int64_t batch, int64_t n_ev
     for (int32_t e0 = 0; e0 < n_ev; e0 += kMcRing) {
         if (__all(c2 >= n_cal)) break;
         EvT r[kMcRing];
-#pragma unroll
-        for (int k = 0; k < kMcRing; ++k) r[k] = row(e0 + k);
-        pad(e0, r);
+        load_event_block<kMcRing, kMcNtl>(ev, batch, lane, e0, n_ev, r);
 #pragma unroll
         for (int k = 0; k < kMcRing; ++k) {
             const EvT v4 = r[k];
@@ -250,12 +231,7 @@ __global__ __launch_bounds__(kMcBlock) void k_magcal_apply(int64_t batch, int64_
         for (int k = 0; k < kApplyRing; ++k) {
             if (e0 + k >= r1) break;  // uniform
             const EvT v4 = r[k];
-            uint32_t ty;
-            if constexpr (EV64)
-                ty = ev64_type(v4);
-            else
-                ty = __float_as_uint(v4.w) & 3u;
-            if (ty != kEvMag) continue;
+            if (event_type(v4) != kEvMag) continue;
             const double x = (double)v4.x - c[0], y = (double)v4.y - c[1], z = (double)v4.z - c[2];
             const double ox = c[3] * x + c[4] * y + c[5] * z, oy = c[6] * x + c[7] * y + c[8] * z,
                          oz = c[9] * x + c[10] * y + c[11] * z;

@@ -19,6 +19,10 @@
 // decimal Float.toString printed (MessageSender.java:222-227), in general not the f32 itself -- so only
 // the FP64 form carries the server's own input values; the state machine and the record arithmetic are
 // the same code for both.
+//
+// The event accessors (event_type, is_message, load_event, null_event) and the two readers of an event
+// plane (load_event_block, event_ring) are here too: phases 1 and 2 (pekf_magcal.hip, k_frontend_init)
+// read the same planes.
 #pragma once
 
 #include "pekf_internal.hpp"
@@ -96,7 +100,9 @@ struct RawRecT<V3> {
 // magnitude < 2^51, so its two lowest mantissa bits are zero) with the type in those two bits (3: a
 // message no sensor takes).  Absolute times: any gap or clock step is just the next event's time.  No
 // message at all (padding) is w = the bits of -0.0 with type 3, which no time packs to.
-__device__ __forceinline__ uint32_t ev64_type(const double4 &e) {
+// The type of an event, in either form (kEvAcc / kEvGyro / kEvMag, or 3: no sensor's).
+__device__ __forceinline__ uint32_t event_type(const float4 &e) { return __float_as_uint(e.w) & 3u; }
+__device__ __forceinline__ uint32_t event_type(const double4 &e) {
     return (uint32_t)__double_as_longlong(e.w) & 3u;
 }
 __device__ __forceinline__ double ev64_time(const double4 &e) {
@@ -108,6 +114,9 @@ __device__ __forceinline__ double4 ev64_null() { return make_double4(0.0, 0.0, 0
 __device__ __forceinline__ bool ev64_none(const double4 &e) {
     return (unsigned long long)__double_as_longlong(e.w) == kEv64None;
 }
+// whether an event is a message of the phone (not a time event / not the no-message event)
+__device__ __forceinline__ bool is_message(const float4 &e) { return __float_as_uint(e.w) != PEKF_EV_TIME; }
+__device__ __forceinline__ bool is_message(const double4 &e) { return !ev64_none(e); }
 
 // The padding event of either form: f32 -- a zero-step time event {0, 0, 0, word 3}; FP64 -- ev64_null.
 template <typename EvT>
@@ -137,6 +146,61 @@ __device__ __forceinline__ double4 load_event(const double4 *q) {
         return make_double4(lo.x, lo.y, hi.x, hi.y);
     } else {
         return *q;
+    }
+}
+
+// The two readers of an event plane ev[n_ev][batch], one lane per column.  Both clamp the row to the last
+// event, so the loads past the end read a valid row and need no predicate, and replace the rows at or past
+// n_ev by null events, which move no state in any phase, so no exit sits inside a caller's unrolled body
+// (an exit per event made the compiler copy the ring on the back edge, behind a wait for the loads just
+// issued).  32-bit event counters (n_ev < 2^30, checked on the host) keep the wave-uniform bounds tests
+// scalar compares, where 64-bit ones took a VALU move and compare each.
+template <bool NT, typename EvT>
+__device__ __forceinline__ EvT load_event_row(const EvT *ev, int64_t batch, uint32_t lane, int32_t e, int32_t n_ev) {
+    return load_event<NT>(ev + (int64_t)(e < n_ev ? e : n_ev - 1) * batch + lane);
+}
+
+// Block-wise: rows e0 .. e0 + N - 1 of the lane's column, every load issued before the first is used
+// (phases 1 and 2: the loop body is a few adds, so without it each wave would wait out one memory latency
+// per event).
+template <int N, bool NT, typename EvT>
+__device__ __forceinline__ void load_event_block(const EvT *ev, int64_t batch, uint32_t lane, int32_t e0, int32_t n_ev,
+                                                 EvT (&r)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = load_event_row<NT>(ev, batch, lane, e0 + k, n_ev);
+    if (e0 + N > n_ev) {  // uniform: the last block only
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            if (e0 + k >= n_ev) r[k] = null_event<EvT>();
+    }
+}
+
+// Load-ahead: the events stream through a register ring of kRing rows loaded kRing events ahead, the loop
+// unrolled by kRing so every ring index is static.  on_event(k, event) runs for every event, k its place
+// in the block (a constant once unrolled); after_block(last) after each whole block of kRing, last: it
+// held the final event.  The last, partial block is padded once per launch.  (The body sits inside
+// `if (n_ev > 0)`: an early return instead cost k_frontend two VGPRs, profiles/r9/one_reader/.)
+template <int kRing, bool NT, typename EvT, typename OnEvent, typename AfterBlock>
+__device__ __forceinline__ void event_ring(const EvT *ev, int64_t batch, uint32_t lane, int32_t n_ev,
+                                           OnEvent &&on_event, AfterBlock &&after_block) {
+    if (n_ev > 0) {
+        EvT ring[kRing];
+#pragma unroll
+        for (int k = 0; k < kRing; ++k) ring[k] = load_event_row<NT>(ev, batch, lane, k, n_ev);
+        for (int32_t e0 = 0; e0 < n_ev; e0 += kRing) {
+            if (e0 + kRing > n_ev) {  // uniform, once per launch
+#pragma unroll
+                for (int k = 0; k < kRing; ++k)
+                    if (e0 + k >= n_ev) ring[k] = null_event<EvT>();
+            }
+#pragma unroll
+            for (int k = 0; k < kRing; ++k) {
+                const EvT v4 = ring[k];
+                ring[k] = load_event_row<NT>(ev, batch, lane, e0 + k + kRing, n_ev);
+                on_event(k, v4);
+            }
+            after_block(e0 + kRing >= n_ev);
+        }
     }
 }
 
@@ -243,7 +307,7 @@ struct Phase3T {
     // One FP64 event {x, y, z, bits(t) | type} (PEKF_EV_F64_EVENTS): the sample is the server's double.
     template <typename F>
     __device__ __forceinline__ void event64(const double4 &e, F &&on_done) {
-        step(S{e.x, e.y, e.z}, ev64_type(e), ev64_time(e), on_done);
+        step(S{e.x, e.y, e.z}, event_type(e), ev64_time(e), on_done);
     }
 
     // The state machine for a sample v of type ty at time tn:

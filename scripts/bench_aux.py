@@ -5,7 +5,7 @@
                 16 B read per event + 40 B written per record
   frontend_then_filter   the filter over those records (pekf_run_dev with counts): the split pipeline
   live          pekf_live_dev: the same events -> filter in one launch (no record window); 16 B read per
-                event + the state once (PEKF_AUX_ONLY=live stops after it)
+                event + the state once (PEKF_AUX_ONLY=live stops after it, =side after wahba_stream)
   gyro_chain    pekf_gyro_chain_dev (§8f-3): 16 B read per filter-record
   wahba_stream  pekf_wahba_stream_dev (§8f-3): 24 B read + 32 B written per filter-record
   predict_dev / correct_dev   per-call operators at n = 1M items (device pointers)
@@ -51,6 +51,20 @@ def timed(fn, stream, reps=3):
         e1.sync()
         out.append(e0.elapsed_ms(e1))
     return float(np.median(out))
+
+
+def bench_events(K0=16384, E=1024):
+    """The generated event streams of the front-end measurements (seed 11); PEKF_EV64_CACHE names an .npz that
+    keeps them between the runs of an A/B (scripts/bench_ev64.py reads and writes the same file)."""
+    cache = os.environ.get("PEKF_EV64_CACHE")
+    if cache and os.path.exists(cache):
+        with np.load(cache) as z:
+            return {k: z[k] for k in z.files}
+    log("generating %d x %d events" % (K0, E))
+    ev = synth.generate_events(np.arange(K0), E, seed=11)
+    if cache:
+        np.savez(cache, **ev)
+    return ev
 
 
 def c1_loop():
@@ -116,8 +130,7 @@ def main():
 
     # ---- front-end: 16K generated event streams tiled x64 -> 1,048,576 filters x 1,024 events
     K0, E, tile = 16384, 1024, 64
-    log("generating %d x %d events" % (K0, E))
-    ev = synth.generate_events(np.arange(K0), E, seed=11)
+    ev = bench_events(K0, E)
     planes = np.ascontiguousarray(np.tile(synth.pack_events(ev), (1, tile, 1)))
     K = K0 * tile
     init = np.tile(np.concatenate([ev["init_acc"], ev["init_mag"]], axis=1), (tile, 1))
@@ -208,6 +221,9 @@ def main():
                            "gbs": B * Nw * 56 / (ms * 1e-3) / 1e9, "hbm_frac": B * Nw * 56 / (ms * 1e-3) / 1e9 / HBM}
     log("wahba stream: %.1f ms" % ms)
     del win, out
+    if os.environ.get("PEKF_AUX_ONLY") == "side":
+        print(json.dumps(res))
+        return
 
     # ---- online serving: every launch advances 1M filters by ONE new record; the state X, P and
     # the reference vectors are read and the state written through HBM each launch.  AoS: 40 B

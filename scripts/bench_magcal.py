@@ -27,7 +27,7 @@ sys.path.insert(0, ROOT)
 from poseestimationkf_amd import engine, synth  # noqa: E402
 from poseestimationkf_amd._lib import EV_F64_EVENTS, check, lib  # noqa: E402
 
-from bench_aux import HBM, log, timed  # noqa: E402
+from bench_aux import HBM, bench_events, log, timed  # noqa: E402
 
 
 def tiled_planes(planes, tile, stream):
@@ -77,7 +77,7 @@ def main():
     del evb, ib, tib, sb, rb, tsb
 
     E = 1024
-    ev = synth.generate_events(np.arange(K0), E, seed=11)
+    ev = bench_events(K0, E)
     host = synth.pack_events64(ev, ev["values"].astype(np.float64))
     evb = tiled_planes(host, tile, s)
     del host

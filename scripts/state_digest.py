@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Final (X, P) of a few fused launches -- 40 B records, FP64 records, the fused front-end + filter --
-saved to an .npz and printed as SHA-256 prefixes, to compare two builds of libpekf.so bit for bit
-(select the build with PEKF_LIB=...).
+and the outputs of the kernels beside them -- the side outputs over both record types, phases 1 and 2,
+the front-end's records -- saved to an .npz and printed as SHA-256 prefixes, to compare two builds of
+libpekf.so bit for bit (select the build with PEKF_LIB=...).
 
 usage: python scripts/state_digest.py <out.npz>
 """
@@ -50,6 +51,44 @@ f = engine.BatchedEKF(8192)
 out["live_counts"], out["live_refs"] = f.run_events(ev)
 out["live_X"], out["live_P"] = f.get_state()
 print("live", float(np.abs(out["live_X"]).sum()), flush=True)
+
+# the side outputs over 40 B and FP64 records: 150 records from row 5 of a 64-row window (a tail in both
+# ring depths, the window replayed)
+rec = synth.generate(np.arange(4096), 64, seed=7)
+for name, w in [("side", engine.IMUWindow.from_records(rec)),
+                ("side64", engine.RecordWindow64.from_arrays(rec.gyro.astype(np.float64), rec.dt_ns,
+                                                            rec.acc.astype(np.float64), rec.mag.astype(np.float64),
+                                                            rec.acc0, rec.mag0))]:
+    out[name + "_gyro_q"], out[name + "_gyro_traj"] = w.gyro_chain(n_steps=150, step0=5, want_traj=True)
+    out[name + "_wahba"] = w.wahba_quaternions(n_steps=150, step0=5)
+    print(name, float(np.abs(out[name + "_gyro_q"]).sum()), flush=True)
+# the same with every seventh record's dt escaped to the side plane (the LONGDT gyro chain)
+esc = np.zeros(rec.dtw.shape, bool)
+esc.reshape(-1)[::7] = True
+rec.dtx = np.where(esc, 3.0e9 + (rec.dtw & synth.DT_MASK), 0.0)
+rec.dtw = np.where(esc, rec.dtw | synth.DT_ESCAPE, rec.dtw).astype(np.uint32)
+out["side_esc_gyro_q"], out["side_esc_gyro_traj"] = engine.IMUWindow.from_records(rec).gyro_chain(
+    n_steps=150, step0=5, want_traj=True)
+
+# phases 2 and 3 of the front-end (pekf_frontend_init_ext_dev with stats, pekf_frontend_ext_dev) and phase 1
+# (pekf_magcal_dev), f32 and FP64 events; row counts that leave a partial last block
+ev2 = synth.generate_events(np.arange(4096), 523, seed=8)
+ev1 = synth.generate_calibration_events(4096, 103, seed=3)
+for form in ("f32", "f64"):
+    for k, v in engine.frontend_init(ev2, n_avg=100, events=form).items():
+        out["init_%s_%s" % (form, k)] = v
+    cal = engine.calibrate_magnetometer(ev1, n_cal=100, events=form)
+    for k in ("bias", "W", "fit", "status"):
+        out["magcal_%s_%s" % (form, k)] = cal[k]
+    win, counts = engine.run_frontend(ev, events=form)
+    dt = np.float64 if form == "f64" else np.float32
+    written = np.arange(win.window)[:, None] < counts[None, :]   # the rows past a filter's count are not written
+    for name, buf, width in [("gd", win.gd, 4), ("am", win.am, 4), ("my", win.my, 2)]:
+        out["frontend_%s_%s" % (form, name)] = np.where(written[..., None],
+                                                        buf.download((win.window, win.batch, width), dt), 0)
+    out["frontend_%s_refs" % form] = win.refs.download((win.batch, 6), np.float64)
+    out["frontend_%s_counts" % form] = counts
+    print("front-end", form, int(counts.sum()), flush=True)
 np.savez(sys.argv[1], **out)
 for k in sorted(out):
     print(k, hashlib.sha256(np.ascontiguousarray(out[k]).tobytes()).hexdigest()[:16])

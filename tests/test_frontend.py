@@ -555,6 +555,38 @@ def test_frontend_init_fp64_events_vs_oracle(eng, E, n_avg):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("stats", [True, False])
+@pytest.mark.parametrize("events", ["f32", "f64"])
+@pytest.mark.parametrize("E", [1, 7, 9, 15, 17, 23])
+def test_frontend_init_block_reader_edges(eng, E, events, stats):
+    """Phase 2's 8-row block reader at its edges: planes of less than one block, one row short of and one row
+    past one and two blocks, 70 filters (a partial wave), n_avg = 2, both event forms, with and without the
+    variance pass -- bit for bit the restatement.  Up to 9 events make no filter ready (every output NaN /
+    0); 15, 17 and 23 make some ready and leave others, so both kinds of lane share a wave."""
+    from poseestimationkf_amd import wire
+    K, n_avg = 70, 2
+    ev = synth.generate_events(np.arange(K), E, seed=8)
+    vals = wire.server_values(ev["values"]) if events == "f64" else ev["values"]
+    want = [fe.initial_values(ev["types"][:, k], vals[:, k], ev["times"][:, k], n_avg=n_avg) for k in range(K)]
+    n_ready = sum(bool(o["ready"]) for o in want)
+    assert n_ready == 0 if E <= 9 else 0 < n_ready < K
+    got = eng.frontend_init(ev, n_avg=n_avg, stats=stats, events=events)
+    assert set(got) == {"init", "t_init", "ready"} | ({"gyro_mean", "var_acc", "var_mag", "var_gyro"} if stats else set())
+    for k, o in enumerate(want):
+        assert got["ready"][k] == o["ready"]
+        if not o["ready"]:
+            assert np.isnan(got["init"][k]).all()
+            assert not stats or all(np.isnan(got[name][k]).all() for name in ("gyro_mean", "var_acc", "var_mag", "var_gyro"))
+            continue
+        assert got["t_init"][k] == o["t_init"]
+        assert np.array_equal(got["init"][k], np.array(o["acc"] + o["mag"]))
+        if stats:
+            assert np.array_equal(got["gyro_mean"][k], np.array(o["gyro"]))
+            for name in ("acc", "mag", "gyro"):
+                assert np.array_equal(got["var_" + name][k], np.array(o["var_" + name]))
+
+
+@pytest.mark.gpu
 def test_fp64_event_arguments_are_checked(eng):
     """PEKF_EV_F64_EVENTS takes no time-event, f32-record or dt-side-plane companion."""
     from poseestimationkf_amd._lib import EV_F32_RECORDS, EV_F64_EVENTS, EV_TIME_EVENTS, PekfError, lib, check

@@ -181,6 +181,33 @@ def test_magcal_degenerate_phones(eng, base, base_cal, events):
     assert np.array_equal(got["status"], mc.calibrate(ev["types"], vals, n_cal=N_CAL)["status"])
 
 
+@pytest.mark.parametrize("events", ["f32", "f64"])
+@pytest.mark.parametrize("E", [20, 21, 23, 24, 25])
+def test_magcal_block_reader_edges(eng, golden, E, events):
+    """The 8-row block reader at its edges, n_cal = 20 and 70 phones (a partial wave): 20 messages never fire
+    the fit (status 1 for every phone); with 21 and 23 the firing message, number 21, sits in a partial last
+    block, 24 end on a whole block and 25 leave one row in the last.  Status and bias bit for bit the
+    restatement's, fit and W within the bounds of test_magcal_fixture_parity."""
+    n_cal, phones = 20, 70
+    ev = _with_values64(synth.generate_calibration_events(phones, E, seed=3))
+    model = mc.calibrate(ev["types"], ev["values"], n_cal=n_cal)
+    assert np.all(model["status"] == (1 if E == n_cal else 0))
+    got = eng.calibrate_magnetometer(ev, n_cal=n_cal, events=events)
+    assert np.array_equal(got["status"], model["status"])
+    assert np.array_equal(_bits(got["bias"]), _bits(model["bias"]))
+    assert np.array_equal(got["calibrated"], model["status"] == 0)
+    if E == n_cal:
+        assert np.all(got["bias"] == 0.0) and np.all(got["W"] == np.eye(3)) and np.isnan(got["fit"]).all()
+        return
+    em = mc.fit_error(got["fit"], model["fit"]).max()
+    w = mc.root_residual(got["W"], mc.r_of(got["fit"])).max()
+    print("k_magcal, %d rows (%s events): fit vs the restatement %.3e (16 e_ref = %.3e), root residual %.3e "
+          "(8 w_ref = %.3e)" % (E, events, em, 16 * golden["e_ref"], w, 8 * golden["w_ref"]))
+    assert em <= 16 * golden["e_ref"]
+    assert np.array_equal(_bits(got["W"]), _bits(got["W"].transpose(0, 2, 1)))
+    assert w <= 8 * golden["w_ref"]
+
+
 def _mixed_plane():
     """107 rows x 200 phones of mixed events (acc / gyro / mag, messages no sensor takes, no-message entries),
     some magnetometer samples -0.0; a calibration with a third of the phones not calibrated."""
