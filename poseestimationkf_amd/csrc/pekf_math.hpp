@@ -1004,6 +1004,20 @@ PEKF_DEV Sym4T<T> spd_inverse_schur(const Sym4T<T> &S) {
     return o;
 }
 
+// Upper triangle of s A B for symmetric A and B that commute (so A B is symmetric): the
+// mixed-precision posterior P = r P- S^-1 (ekf_record_step_mixed).  50 operations.
+template <typename T>
+PEKF_DEV Sym4T<T> sym_product_upper(const Sym4T<T> &A, const Sym4T<T> &B, T s) {
+    const T a[4][4] = {{A.a00, A.a01, A.a02, A.a03}, {A.a01, A.a11, A.a12, A.a13},
+                       {A.a02, A.a12, A.a22, A.a23}, {A.a03, A.a13, A.a23, A.a33}};
+    const T b[4][4] = {{B.a00, B.a01, B.a02, B.a03}, {B.a01, B.a11, B.a12, B.a13},
+                       {B.a02, B.a12, B.a22, B.a23}, {B.a03, B.a13, B.a23, B.a33}};
+    auto e = [&](int i, int j) -> T {
+        return s * fma(a[i][3], b[3][j], fma(a[i][2], b[2][j], fma(a[i][1], b[1][j], a[i][0] * b[0][j])));
+    };
+    return {e(0, 0), e(0, 1), e(0, 2), e(0, 3), e(1, 1), e(1, 2), e(1, 3), e(2, 2), e(2, 3), e(3, 3)};
+}
+
 // Closed form of the classical RK4 step + normalisation (ExtendedKalmanFilter.py:25-41),
 // h_w = w/2 (so Omega(h_w) = 0.5*Omega(w), the reference's W).  z = ca x + cb 0.5*Omega(w) x and,
 // since 0.5*Omega(w) is skew with square -|h_w|^2 I, |z|^2 = (ca^2 + cb^2 |h_w|^2) |x|^2 exactly:

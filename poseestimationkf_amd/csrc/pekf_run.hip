@@ -106,8 +106,12 @@ __global__ __launch_bounds__(kRunBlock) void k_run_one(int64_t batch, int64_t wi
             a[0] = va.x; a[1] = va.y; a[2] = va.z;
             m[0] = va.w; m[1] = vm.x; m[2] = vm.y;
         };
-        ekf_record_step<PT>(x, state_norm2(x), P, Wf, step_consts<PT, false>(qs, rs), gy, dtn,
-                            (word & PEKF_MISSING_MAG_BIT) != 0, acc, mag, reload);
+        if constexpr (MIXED)
+            ekf_record_step_mixed<false, true>(x, state_norm2(x), P, Wf, step_consts_mixed(qs, rs), gy, dtn,
+                                               (word & PEKF_MISSING_MAG_BIT) != 0, acc, mag, reload);
+        else
+            ekf_record_step<PT>(x, state_norm2(x), P, Wf, step_consts<PT, false>(qs, rs), gy, dtn,
+                                (word & PEKF_MISSING_MAG_BIT) != 0, acc, mag, reload);
     }
     if (TRAJ && act) {
         double2 *o = reinterpret_cast<double2 *>(traj) + 2 * (int64_t)lane;
@@ -177,7 +181,11 @@ __global__ __launch_bounds__(kRunBlock) void k_update(int64_t batch, const doubl
             rm[i] = mag[3 * b + i];
         }
     };
-    ekf_record_step<PT>(x, state_norm2(x), P, Wf, step_consts<PT, false>(qs, rs), g, dt_ns, miss, a, m, reload);
+    if constexpr (MIXED)
+        ekf_record_step_mixed<false, true>(x, state_norm2(x), P, Wf, step_consts_mixed(qs, rs), g, dt_ns, miss, a, m,
+                                           reload);
+    else
+        ekf_record_step<PT>(x, state_norm2(x), P, Wf, step_consts<PT, false>(qs, rs), g, dt_ns, miss, a, m, reload);
     if (act) prev_t[b] = t;
     if constexpr (SOA) {
         if (act) store_state<true>(Xio, Pio, b, batch, x, P);

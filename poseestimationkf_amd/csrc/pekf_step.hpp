@@ -375,6 +375,84 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> 
     }
 }
 
+// ---- The same record with the covariance recursion in f32 (PEKF_RUN_MIXED_PRECISION) ----
+// The FP64 step's algebra adds P- to rI and takes P = rI - r^2 S^-1 and K = I - r S^-1 as differences
+// from r.  In f32 that rounds the parts of P of size ~q/4 at eps32 r: a relative error ~eps32 r / q in
+// P and, through K, in X (measured: DESIGN.md §4.3).  Here r enters only inside the inverse, and the
+// gain and the posterior are products:
+//   2P- = innovation_cov2 with no r term,  S^-1 / 2 = (2P- + 2rI)^-1,  P = r K = r (2P-)(S^-1 / 2),
+//   X = z + K e = z + P e / r,
+// so every rounding is relative to the quantity it rounds.  2P- is formed in FP64 from the f32 P and
+// rounded once: innovation_cov2's trace-butterfly form cancels (for P ~ cI it is 4|h|^2 c - 2|h|^2 c),
+// its f32 roundings are common to the whole diagonal, and where the gyro term dominates (P+ ~ |h|^2 P)
+// the relative error of P is never forgotten and adds up record after record.  S, its
+// inverse and the product P- S^-1 are f32.  The covariance is carried as P in every launch shape (in the
+// multi-record loop in the reference frame's basis).  P e is formed in FP64 from the f32 P, e = Y - z
+// stays FP64, and RK4, Wahba and the normalisation are the FP64 step's.
+// NORM = false (the multi-record loop) leaves X = z + K e unnormalised, as the FP64 loop does:
+// LAZY is ekf_record_step's.
+struct StepKMixed {
+    double g2, ir;  // 2g, 1 / r
+    float r2, rp;   // 2r, r
+};
+__device__ __forceinline__ StepKMixed step_consts_mixed(double qs, double rs) {
+    return {0.5 * qs, 1.0 / rs, (float)(2.0 * rs), (float)rs};
+}
+template <bool LAZY, bool NORM, typename Ref, typename Reload>
+__device__ __forceinline__ void ekf_record_step_mixed(double *x, double n2, Sym4T<float> &P, const Ref &Wf,
+                                                      const StepKMixed &k, const double *gy, double dt_ns,
+                                                      bool missing, const double *acc, const double *mag,
+                                                      const Reload &reload) {
+    // ---- Prediction (ExtendedKalmanFilter.py:58-68) ----
+    const double n2x = LAZY ? x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3] : n2;
+    const double hw[3] = {0.5 * gy[0], 0.5 * gy[1], 0.5 * gy[2]};  // 0.5*Omega(w) = Omega(w/2)
+    const double th2 = hw[0] * hw[0] + hw[1] * hw[1] + hw[2] * hw[2];
+    double z[4], kk, irk;
+    rk4_closed(x, n2x, dt_ns, hw, th2, z, kk, irk);                      // (:62)
+    const double g2x = LAZY ? ((irk * irk) * kk) * k.g2 : k.g2;          // 2g / |x|^2
+    const Sym4 Pd = {P.a00, P.a01, P.a02, P.a03, P.a11, P.a12, P.a13, P.a22, P.a23, P.a33};
+    const Sym4 Md = innovation_cov2<double>(Pd, hw, gy, th2, x, LAZY ? 1.0 : n2, k.g2, 0.0, g2x);  // 2P- (:61)
+    const Sym4T<float> M2 = {(float)Md.a00, (float)Md.a01, (float)Md.a02, (float)Md.a03, (float)Md.a11,
+                             (float)Md.a12, (float)Md.a13, (float)Md.a22, (float)Md.a23, (float)Md.a33};
+    if (missing) {  // Wahba-skip: X = z, P = P-
+        x[0] = z[0]; x[1] = z[1]; x[2] = z[2]; x[3] = z[3];
+        const float hf = 0.5f;
+        P = {hf * M2.a00, hf * M2.a01, hf * M2.a02, hf * M2.a03, hf * M2.a11,
+             hf * M2.a12, hf * M2.a13, hf * M2.a22, hf * M2.a23, hf * M2.a33};
+        return;
+    }
+    Sym4T<float> S2 = M2;  // 2S = 2P- + 2rI (:63)
+    S2.a00 += k.r2; S2.a11 += k.r2; S2.a22 += k.r2; S2.a33 += k.r2;
+    const Sym4T<float> Si = spd_inverse_schur<float, true, false>(S2);    // S^-1 / 2
+    // ---- Correction (ExtendedKalmanFilter.py:70-80) ----
+    const double ka = fabs(acc[2]);  // (:71)
+    double v[4], sc;                 // Wahba.py:8-47 + the flip of :73-75: Y = v sc
+    if constexpr (std::is_same<Ref, Frame>::value) {
+        Frame Vf;
+        make_frame<1>(acc, mag, Vf, 1.0 - ka);
+        wahba_quat_toward<1>(Wf, Vf, ka, 1.0 - ka, z, v, sc, reload);
+    } else {
+        wahba_quat_toward<1>(Wf, acc, mag, ka, 1.0 - ka, z, v, sc, reload);
+    }
+    P = sym_product_upper(M2, Si, k.rp);  // P = P- - K P- = r K (:66, :78)
+    const double e0 = fma_sub(v[0], sc, z[0]), e1 = fma_sub(v[1], sc, z[1]);
+    const double e2 = fma_sub(v[2], sc, z[2]), e3 = fma_sub(v[3], sc, z[3]);
+    const double p00 = P.a00, p01 = P.a01, p02 = P.a02, p03 = P.a03, p11 = P.a11;
+    const double p12 = P.a12, p13 = P.a13, p22 = P.a22, p23 = P.a23, p33 = P.a33;
+    const double u0 = p00 * e0 + p01 * e1 + p02 * e2 + p03 * e3;
+    const double u1 = p01 * e0 + p11 * e1 + p12 * e2 + p13 * e3;
+    const double u2 = p02 * e0 + p12 * e1 + p22 * e2 + p23 * e3;
+    const double u3 = p03 * e0 + p13 * e1 + p23 * e2 + p33 * e3;
+    const double x0 = fma(u0, k.ir, z[0]), x1 = fma(u1, k.ir, z[1]);      // X = z + K e (:77)
+    const double x2 = fma(u2, k.ir, z[2]), x3 = fma(u3, k.ir, z[3]);
+    if (NORM) {  // (:79)
+        const double in = rsqrt<true>(x0 * x0 + x1 * x1 + x2 * x2 + x3 * x3);
+        x[0] = x0 * in; x[1] = x1 * in; x[2] = x2 * in; x[3] = x3 * in;
+    } else {
+        x[0] = x0; x[1] = x1; x[2] = x2; x[3] = x3;
+    }
+}
+
 // A multi-record launch runs the filter in its reference frame's own basis (RefW in pekf_math.hpp:
 // the same filter, with Wahba's rotation 24 operations cheaper per record) with the covariance
 // carried as N, P = rI + beta D N D (StepK); the state is rotated in once and out once per launch.
@@ -385,9 +463,11 @@ __device__ __forceinline__ void to_ref_basis(const double *qw, double *x, Sym4T<
     qmul_left<true>(qw, x, xw);
     x[0] = xw[0]; x[1] = xw[1]; x[2] = xw[2]; x[3] = xw[3];
     P = sym_rotate<true>(qw, P);
-    const PT ib = (PT)(1.0 / (kSqrt2 * rs)), rp = (PT)rs;
-    P = {(P.a00 - rp) * ib, P.a01 * ib, -P.a02 * ib, -P.a03 * ib, (P.a11 - rp) * ib,
-         -P.a12 * ib, -P.a13 * ib, (P.a22 - rp) * ib, P.a23 * ib, (P.a33 - rp) * ib};
+    if constexpr (std::is_same<PT, double>::value) {  // the mixed loop carries P itself (ekf_record_step_mixed)
+        const PT ib = (PT)(1.0 / (kSqrt2 * rs)), rp = (PT)rs;
+        P = {(P.a00 - rp) * ib, P.a01 * ib, -P.a02 * ib, -P.a03 * ib, (P.a11 - rp) * ib,
+             -P.a12 * ib, -P.a13 * ib, (P.a22 - rp) * ib, P.a23 * ib, (P.a33 - rp) * ib};
+    }
 }
 // The launch's prologue: the reference pair's Frame as the RefW (HOLD: q_W held through the loop, for
 // trajectory output) or the RefWLazy (q_W recomputed from `pair` at the launch's end and in the rare
@@ -422,9 +502,11 @@ __device__ __forceinline__ void ref_to_world(const RW &Wr, const double *x, doub
 // from_ref_basis: back at the launch's end, X normalised.
 template <typename PT, typename RW>
 __device__ __forceinline__ void from_ref_basis(const RW &Wr, double *x, Sym4T<PT> &P, double rs) {
-    const PT be = (PT)(kSqrt2 * rs), rp = (PT)rs;
-    P = {fma(be, P.a00, rp), be * P.a01, -be * P.a02, -be * P.a03, fma(be, P.a11, rp),
-         -be * P.a12, -be * P.a13, fma(be, P.a22, rp), be * P.a23, fma(be, P.a33, rp)};
+    if constexpr (std::is_same<PT, double>::value) {
+        const PT be = (PT)(kSqrt2 * rs), rp = (PT)rs;
+        P = {fma(be, P.a00, rp), be * P.a01, -be * P.a02, -be * P.a03, fma(be, P.a11, rp),
+             -be * P.a12, -be * P.a13, fma(be, P.a22, rp), be * P.a23, fma(be, P.a33, rp)};
+    }
     double xo[4], qw[4];
     ref_to_world(Wr, x, xo, qw);
     x[0] = xo[0]; x[1] = xo[1]; x[2] = xo[2]; x[3] = xo[3];
@@ -448,7 +530,7 @@ __device__ __forceinline__ void from_ref_basis(const RW &Wr, double *x, Sym4T<PT
 // fraction, no escape word; every record carries a magnetometer sample, as a log's always does).
 // MIXED = false: every operation in FP64 (the headline path).
 // MIXED = true (opt-in, PEKF_RUN_MIXED_PRECISION): the covariance recursion (P-, S^-1, K, P)
-// in FP32 while RK4, Wahba, R->q and the X update stay FP64 (~2e-8 vs FP64).
+// in FP32 while RK4, Wahba, R->q and the X update stay FP64 (ekf_record_step_mixed).
 // COUNTS: filter b applies only its first counts[b] records of the launch (a separate
 // instantiation so the uniform-length path carries no per-step lane predicate).
 // PIN: the Schur-inverse-first schedule of the multi-record loop (ekf_record_step, launch_run_multi).
@@ -519,8 +601,12 @@ __global__ __launch_bounds__(kRunBlock) PEKF_RUN_ATTR void k_run(int64_t batch, 
                 missing = (word & PEKF_MISSING_MAG_BIT) != 0;
             }
             auto reload = [&](double *a, double *m) { rows.reload(kLag, a, m); };  // rare: this record again
-            ekf_record_step<PT, true, decltype(lazy)::value, !MIXED, PIN, HOIST && !MIXED>(
-                x, n2, P, Wr, step_consts<PT, true>(qs, rs), gy, dtn, missing, acc, mag, reload);
+            if constexpr (MIXED)
+                ekf_record_step_mixed<decltype(lazy)::value, false>(x, n2, P, Wr, step_consts_mixed(qs, rs), gy, dtn,
+                                                                    missing, acc, mag, reload);
+            else
+                ekf_record_step<PT, true, decltype(lazy)::value, true, PIN, HOIST>(
+                    x, n2, P, Wr, step_consts<PT, true>(qs, rs), gy, dtn, missing, acc, mag, reload);
         }
         if (TRAJ) {
             // a filter with no records in this launch (COUNTS) repeats its stored X unchanged

@@ -4,7 +4,8 @@
 Each case draws a batch (1-300 filters), a window (1-48 rows) and a run of 1-3 windows' worth of
 records, cut into launches of random length at a random start row (launches of one record take the
 online instantiation, longer ones the multi-record kernel; the rows wrap in the window).  It also
-draws per-launch record counts, trajectory output, AoS or SoA state, FP64 or mixed precision, the
+draws per-launch record counts, trajectory output, AoS or SoA state, FP64 or mixed precision (judged against
+the f32 yardstick of tests/mixed_numpy.py, X and P), the
 batched engine or the native filter handle, a random initial state, q and r, dt gaps up to 2 s,
 missing magnetometer samples and escaped dts (negative, 2^31 ns and more, fractional).  Every
 filter's expected state is the oracle run over exactly the records that filter applied, in order
@@ -29,9 +30,18 @@ sys.path.insert(0, ROOT)
 
 from oracle import ekf_numpy, oracle_c  # noqa: E402  (the checkers)
 from poseestimationkf_amd import engine, synth  # noqa: E402
+from tests import mixed_numpy  # noqa: E402  (the f32 yardstick and the acceptance rule of the mixed path)
 
 TOL_F64 = 1e-9      # |X - X_oracle|, and |P - P_oracle| / max(1, r, max|P_oracle|): the FP64 path
-TOL_MIXED_X = 2e-5  # the opt-in mixed-precision path (covariance in f32)
+# The opt-in mixed-precision path (covariance in f32) is judged as tests/test_mixed_precision.py judges it:
+# X (final and trajectories) and the final P may err from the oracle up to mixed_numpy.FACTOR x as far as the
+# f32 yardstick, mixed_numpy.run_filter_pt(np.float32) over the same records of every filter, does.  A case
+# here can be one filter and one record, where the yardstick's own error may happen to vanish, so its error
+# counts as no less than what the format alone costs: for P one f32 ulp of max|P| (2^-23: an entry rounded
+# twice to nearest), for X = z + K e one ulp of a gain |K| <= 1 at the largest |e| = |Y - z| = 2 (2^-23).
+# TOL_MIXED_X stays as the outer cap on X.
+TOL_MIXED_X = 2e-5
+MIXED_FLOOR = (2.0 ** -23, 2.0 ** -23)   # eX, eP
 # A case whose covariance grows past this (long runs of Prediction-only records with large |w| dt:
 # GetJacobian_A is not orthogonal, so P- grows by |A|^2 per record) is ill-conditioned: there the
 # gain K = P-(P- + rI)^-1 rounds to I and X follows rounding noise.  Such cases, and those where
@@ -120,8 +130,9 @@ def _filter_records(case, b, rows):
                          None if rec.dtx is None else rec.dtx[rows, b:b + 1])
 
 
-def expected_numpy(case, b):
-    """expected() for filter b through the NumPy restatement: (X (4,), P (4,4), [traj (L,4) or None])."""
+def expected_numpy(case, b, pt=None):
+    """expected() for filter b through the NumPy restatement: (X (4,), P (4,4), [traj (L,4) or None]);
+    pt: through mixed_numpy.run_filter_pt with the covariance side in that dtype instead."""
     X = np.array([1.0, 0.0, 0.0, 0.0]) if case["X0"] is None else case["X0"][b].copy()
     P = np.eye(4) if case["P0"] is None else case["P0"][b].copy()
     trajs = []
@@ -131,8 +142,13 @@ def expected_numpy(case, b):
         if c > 0:
             sub = _filter_records(case, b, (s + np.arange(c)) % case["W"])
             g, dt, a, m = sub.filter(0)
-            X, P, t = ekf_numpy.run_filter(g, dt, a, m, sub.acc0[0], sub.mag0[0], q=case["q"], r=case["r"], X0=X,
-                                           P0=P, missing=sub.missing[:, 0], record=want)
+            if pt is None:
+                X, P, t = ekf_numpy.run_filter(g, dt, a, m, sub.acc0[0], sub.mag0[0], q=case["q"], r=case["r"], X0=X,
+                                               P0=P, missing=sub.missing[:, 0], record=want)
+            else:
+                t, Ps = mixed_numpy.run_filter_pt(g, dt, a, m, sub.acc0[0], sub.mag0[0], case["q"], case["r"], pt,
+                                                  X0=X, P0=P, missing=sub.missing[:, 0])
+                X, P = t[-1], Ps[-1]
             if want:
                 tr[:c] = np.asarray(t).reshape(c, 4)
         if want:
@@ -159,6 +175,23 @@ def within_spread(case, Xg, Pg, tg, Xe, Pe, te, scale):
             if np.any(err >= np.maximum(TOL_F64, SPREAD * spread)):
                 return False
     return True
+
+
+def mixed_errors(case, Xg, Pg, tg, Xe, Pe, te):
+    """((eX_gpu, eP_gpu), (eX_ref, eP_ref)) of a mixed case, the yardstick's no less than MIXED_FLOOR."""
+    K = case["K"]
+    Xy, Py, ty = np.empty((K, 4)), np.empty((K, 4, 4)), [None if e is None else np.empty_like(e) for e in te]
+    for b in range(K):
+        Xy[b], Py[b], tb = expected_numpy(case, b, np.float32)
+        for t, y in zip(tb, ty):
+            if y is not None:
+                y[:, b] = t
+
+    def errs(X, P, trs):
+        eX, eP = mixed_numpy.errors(X, P, Xe, Pe)
+        return max([eX] + [float(np.abs(t - e).max()) for t, e in zip(trs, te) if e is not None]), eP
+    e_ref = errs(Xy, Py, ty)
+    return errs(Xg, Pg, tg), tuple(max(e, f) for e, f in zip(e_ref, MIXED_FLOOR))
 
 
 def run_gpu(case):
@@ -244,7 +277,10 @@ def main(argv=None):
             else:
                 worst = max(worst, ex, ep, et)
         else:
-            ok = ex < TOL_MIXED_X and et < TOL_MIXED_X
+            e_got, e_ref = mixed_errors(case, Xg, Pg, tg, Xe, Pe, te)
+            ok = ex < TOL_MIXED_X and et < TOL_MIXED_X and mixed_numpy.accept(e_got, e_ref)
+            print("case %d mixed: eX_ref %.3e eP_ref %.3e eX_gpu %.3e eP_gpu %.3e  %s"
+                  % ((i,) + e_ref + e_got + (describe(case),)), flush=True)
         if not ok:
             fails += 1
             print("MISMATCH case %d: |dX| %.3e |dP|/scale %.3e |dtraj| %.3e max|P| %.2e  %s"
