@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <initializer_list>
@@ -123,59 +124,74 @@ class Staging {
     int device_ = -1;
 };
 
-// One host-pointer operator call: kernel(n, inputs..., outputs..., [status plane,] Done) over n items.
-// An operand is its host pointer and its doubles per item.  ONE is the operator's n = 1 route (call1<OP>
-// of pekf_percall.hip) or nullptr; ERR is the code a non-zero entry of the kernel's status plane maps to,
-// with err_msg, or PEKF_OK for a kernel without a status plane.  The caller has checked its arguments.
-struct OpIn {
-    const double *ptr;
-    size_t width;
+// A per-call operator is one table entry Op (pekf_percall.hip holds the table and states the form): Op::In and
+// Op::Out are Widths<...>, the doubles per item of each operand in ABI order; everything else about the layout
+// -- offsets, totals, the widest operand -- is derived from them here.
+template <int... W>
+struct Widths {
+    static constexpr int count = sizeof...(W);
+    static constexpr int total = (W + ... + 0);
+    static constexpr int widest = std::max({W...});
+    static constexpr int w(int k) {
+        const int a[] = {W...};
+        return a[k];
+    }
+    static constexpr int off(int k) {  // operand k's first double within an item's concatenated operands
+        int s = 0;
+        for (int j = 0; j < k; ++j) s += w(j);
+        return s;
+    }
 };
-struct OpOut {
-    double *ptr;
-    size_t width;
-};
-using Call1Fn = int (*)(std::initializer_list<HostArg>, std::initializer_list<HostOut>, int32_t *);
 
-template <int BLOCK, Call1Fn ONE, int ERR, class K, size_t NI, size_t NO, size_t... I, size_t... O>
-static int staged_call(K kernel, const char *name, int64_t n, const OpIn (&in)[NI], const OpOut (&out)[NO],
-                       const char *err_msg, std::index_sequence<I...>, std::index_sequence<O...>) {
-    constexpr bool kStatus = ERR != PEKF_OK;
+// An operator's operand pointers (host or device), as its entry points take them.
+template <class Op>
+struct OpPtrs {
+    const double *in[Op::In::count];
+    double *out[Op::Out::count];
+};
+template <class Op>
+using OpKernel = void (*)(int64_t, OpPtrs<Op>, int32_t *, Done);
+template <class Op>
+using Call1Fn = int (*)(const OpPtrs<Op> &, int32_t *);
+
+// One host-pointer operator call: kernel(n, device operands, status plane, Done) over n items.  ONE is the
+// operator's n = 1 route (call1<Op> of pekf_percall.hip) or nullptr; Op::kErr is the code a non-zero entry of the
+// status plane maps to, with Op::kMsg, or PEKF_OK for a kernel without one.  The caller has checked its arguments.
+template <class Op, int BLOCK, Call1Fn<Op> ONE, size_t... I, size_t... O>
+static int staged_call(OpKernel<Op> kernel, int64_t n, const OpPtrs<Op> &a, std::index_sequence<I...>,
+                       std::index_sequence<O...>) {
+    using In = typename Op::In;
+    using Out = typename Op::Out;
+    constexpr bool kStatus = Op::kErr != PEKF_OK;
     if (int st = require_device()) return st;
-    const size_t b = (size_t)n * sizeof(double);
     if constexpr (ONE != nullptr) {
         if (n == 1) {
             int32_t st1 = 0;
-            if (int st = ONE({{in[I].ptr, in[I].width * b}...}, {{out[O].ptr, out[O].width * b}...}, &st1)) return st;
-            return kStatus && st1 ? set_error(ERR, "%s", err_msg) : PEKF_OK;
+            if (int st = ONE(a, &st1)) return st;
+            return kStatus && st1 ? set_error(Op::kErr, "%s", Op::kMsg) : PEKF_OK;
         }
     }
+    const size_t b = (size_t)n * sizeof(double);
     Staging &s = Staging::get();
     // the status plane follows the outputs; without one it is an empty plane that nothing reads or writes
     std::vector<int32_t> status(kStatus ? (size_t)n : 0);
     const size_t sb = status.size() * sizeof(int32_t);
-    void *din[NI], *dout[NO + 1];
-    if (int st = s.stage_in({{in[I].ptr, in[I].width * b}...}, {out[O].width * b..., sb}, din, dout)) return st;
-    auto launch = [&](auto... tail) {
-        hipLaunchKernelGGL(kernel, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s.stream(), n,
-                           static_cast<const double *>(din[I])..., static_cast<double *>(dout[O])..., tail...);
-    };
-    if constexpr (kStatus)
-        launch(static_cast<int32_t *>(dout[NO]), s.done(grid_for(n, BLOCK)));
-    else
-        launch(s.done(grid_for(n, BLOCK)));
-    if (int st = launched(name)) return st;
-    if (int st = s.stage_out({{out[O].ptr, out[O].width * b}..., {status.data(), sb}}, dout)) return st;
+    void *din[In::count], *dout[Out::count + 1];
+    if (int st = s.stage_in({{a.in[I], In::w(I) * b}...}, {Out::w(O) * b..., sb}, din, dout)) return st;
+    const OpPtrs<Op> d = {{static_cast<const double *>(din[I])...}, {static_cast<double *>(dout[O])...}};
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s.stream(), n, d,
+                       kStatus ? static_cast<int32_t *>(dout[Out::count]) : nullptr, s.done(grid_for(n, BLOCK)));
+    if (int st = launched(Op::kName)) return st;
+    if (int st = s.stage_out({{a.out[O], Out::w(O) * b}..., {status.data(), sb}}, dout)) return st;
     for (int32_t v : status)
-        if (v) return set_error(ERR, "%s", err_msg);
+        if (v) return set_error(Op::kErr, "%s", Op::kMsg);
     return PEKF_OK;
 }
 
-template <int BLOCK, Call1Fn ONE = nullptr, int ERR = PEKF_OK, class K, size_t NI, size_t NO>
-static int staged_call(K kernel, const char *name, int64_t n, const OpIn (&in)[NI], const OpOut (&out)[NO],
-                       const char *err_msg = nullptr) {
-    return staged_call<BLOCK, ONE, ERR>(kernel, name, n, in, out, err_msg, std::make_index_sequence<NI>{},
-                                        std::make_index_sequence<NO>{});
+template <class Op, int BLOCK, Call1Fn<Op> ONE = nullptr>
+static int staged_call(OpKernel<Op> kernel, int64_t n, const OpPtrs<Op> &a) {
+    return staged_call<Op, BLOCK, ONE>(kernel, n, a, std::make_index_sequence<Op::In::count>{},
+                                       std::make_index_sequence<Op::Out::count>{});
 }
 
 // Stops the resident per-call service kernel (pekf_percall.hip) of every device, e.g. before a

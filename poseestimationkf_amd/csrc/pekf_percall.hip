@@ -1,9 +1,12 @@
 // pekf_percall.hip -- per-call operators behind the drop-in Python API (one thread per item).
 //
 // These keep the reference's dense formulation (ExtendedKalmanFilter.py, Wahba.py) so
-// each call matches NumPy to rounding; the fused time-loop kernel is pekf_run.hip.  The batched
-// kernels move their per-item operands through WaveTile (pekf_tile.hpp): coalesced block reads
-// and writes, transposed through LDS; the d_* bodies work on per-lane copies.
+// each call matches NumPy to rounding; the fused time-loop kernel is pekf_run.hip.  Each fixed-width
+// operator is one entry of the operator table below: its operand widths, its status mapping, its kernel
+// name and its lane-private body.  The batched kernel k_op<Op>, the n = 1 routes (k_call1<Op>, the
+// resident service) and the host entry points all read the operand layout from that entry.  The batched
+// kernel moves the per-item operands through WaveTile (pekf_tile.hpp): coalesced block reads and writes,
+// transposed through LDS; the bodies work on per-lane copies.
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -19,31 +22,6 @@ namespace pekf {
 
 constexpr int kBlock = 256;
 
-__device__ __forceinline__ void d_rk4(int64_t i, const double *q0, const double *dt,
-                                               const double *w, double *out) {
-    rk4_literal(q0 + 4 * i, dt[i], w + 3 * i, out + 4 * i);
-}
-
-// Pool of LDS for the WaveTiles of a block whose widest operand has W doubles per item.
-#define PEKF_TILE(t, W, n)                                                  \
-    __shared__ double pool_[kBlock / kWave * tile_doubles<W>()];           \
-    const WaveTile t(pool_, tile_doubles<W>(), (n))
-
-__global__ __launch_bounds__(kBlock) void k_rk4(int64_t n, const double *q0, const double *dt,
-                                               const double *w, double *out, Done done) {
-    PEKF_TILE(t, 4, n);
-    double cq[4], cd[1], cw[3], vq[4], vd[1], vw[3], o[4];
-    t.gather(q0, cq);
-    t.gather(dt, cd);
-    t.gather(w, cw);
-    t.to_lanes(cq, vq);
-    t.to_lanes(cd, vd);
-    t.to_lanes(cw, vw);
-    d_rk4(0, vq, vd, vw, o);
-    t.store(out, o);
-    done.signal();  // the whole block reaches this point (no early return)
-}
-
 __device__ __forceinline__ void d_norm(int64_t i, int64_t len, const double *a,
                                                 double *out) {
     double s = 0.0;
@@ -51,6 +29,7 @@ __device__ __forceinline__ void d_norm(int64_t i, int64_t len, const double *a,
     out[i] = sqrt(s);
 }
 
+// written out: len is a run-time width, so norm is no table entry and has no n = 1 route
 __global__ __launch_bounds__(kBlock) void k_norm(int64_t n, int64_t len, const double *a,
                                                 double *out, Done done) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -58,53 +37,70 @@ __global__ __launch_bounds__(kBlock) void k_norm(int64_t n, int64_t len, const d
     done.signal();  // the whole block reaches this point (no early return)
 }
 
-__device__ __forceinline__ void d_jac_a(int64_t i, const double *w, double *A) {
-    omega_half(w + 3 * i, A + 16 * i);
-}
+// ---------------------------------------------------------------------------------------------
+// The operator table.  An entry states
+//   In, Out   doubles per item of each input and output, in ABI order (Widths<>, pekf_internal.hpp:
+//             offsets, totals and the widest operand follow from them);
+//   kErr/kMsg the error a non-zero status maps to (PEKF_OK: the operator has no status plane);
+//   kName     the batched kernel's name in launch errors;
+//   body      the operator on one item: a pointer per input (lane-private) and per output, then a sink
+//             and the status word.  The body tells the sink that output k is complete with
+//             done.template put<k>() as soon as it is -- a tile store in k_op, nothing in the n = 1 routes,
+//             whose output pointers are the destination -- so that a wide result does not stay live across
+//             the work that follows it.
 
-__global__ __launch_bounds__(kBlock) void k_jac_a(int64_t n, const double *w, double *A, Done done) {
-    PEKF_TILE(t, 16, n);
-    double vw[3], o[16];
-    t.load(w, vw);
-    d_jac_a(0, vw, o);
-    t.store(A, o);
-    done.signal();  // the whole block reaches this point (no early return)
-}
+struct OpRk4 {
+    using In = Widths<4, 1, 3>;  // q0, dt, w
+    using Out = Widths<4>;
+    static constexpr int kErr = PEKF_OK;
+    static constexpr const char *kMsg = nullptr, *kName = "k_rk4";
+    template <class S>
+    __device__ __forceinline__ static void body(const double *q0, const double *dt, const double *w, double *q,
+                                                const S &done, int32_t *) {
+        rk4_literal(q0, dt[0], w, q);
+        done.template put<0>();
+    }
+};
 
-__device__ __forceinline__ void d_jac_b(int64_t i, const double *q, double *J) {
-    xi_half(q + 4 * i, J + 12 * i);
-}
+struct OpJacA {
+    using In = Widths<3>;  // w
+    using Out = Widths<16>;
+    static constexpr int kErr = PEKF_OK;
+    static constexpr const char *kMsg = nullptr, *kName = "k_jac_a";
+    template <class S>
+    __device__ __forceinline__ static void body(const double *w, double *A, const S &done, int32_t *) {
+        omega_half(w, A);
+        done.template put<0>();
+    }
+};
 
-__global__ __launch_bounds__(kBlock) void k_jac_b(int64_t n, const double *q, double *J, Done done) {
-    PEKF_TILE(t, 12, n);
-    double vq[4], o[12];
-    t.load(q, vq);
-    d_jac_b(0, vq, o);
-    t.store(J, o);
-    done.signal();  // the whole block reaches this point (no early return)
-}
+struct OpJacB {
+    using In = Widths<4>;  // q
+    using Out = Widths<12>;
+    static constexpr int kErr = PEKF_OK;
+    static constexpr const char *kMsg = nullptr, *kName = "k_jac_b";
+    template <class S>
+    __device__ __forceinline__ static void body(const double *q, double *J, const S &done, int32_t *) {
+        xi_half(q, J);
+        done.template put<0>();
+    }
+};
 
 // conj(q1) (x) q2 as the reference's 4x4 left-multiplication (ExtendedKalmanFilter.py:16-23)
-__device__ __forceinline__ void d_comparator(int64_t i, const double *q1,
-                                                      const double *q2, double *out) {
-    const double *a = q1 + 4 * i, *b = q2 + 4 * i;
-    const double c0 = a[0], c1 = -a[1], c2 = -a[2], c3 = -a[3];
-    const double L[16] = {c0, -c1, -c2, -c3, c1, c0, -c3, c2, c2, c3, c0, -c1, c3, -c2, c1, c0};
-    matmul<4, 4, 1>(L, b, out + 4 * i);
-}
-
-__global__ __launch_bounds__(kBlock) void k_comparator(int64_t n, const double *q1,
-                                                      const double *q2, double *out, Done done) {
-    PEKF_TILE(t, 4, n);
-    double c1[4], c2[4], v1[4], v2[4], o[4];
-    t.gather(q1, c1);
-    t.gather(q2, c2);
-    t.to_lanes(c1, v1);
-    t.to_lanes(c2, v2);
-    d_comparator(0, v1, v2, o);
-    t.store(out, o);
-    done.signal();  // the whole block reaches this point (no early return)
-}
+struct OpComparator {
+    using In = Widths<4, 4>;  // q1, q2
+    using Out = Widths<4>;
+    static constexpr int kErr = PEKF_OK;
+    static constexpr const char *kMsg = nullptr, *kName = "k_comparator";
+    template <class S>
+    __device__ __forceinline__ static void body(const double *a, const double *b, double *q, const S &done,
+                                                int32_t *) {
+        const double c0 = a[0], c1 = -a[1], c2 = -a[2], c3 = -a[3];
+        const double L[16] = {c0, -c1, -c2, -c3, c1, c0, -c3, c2, c2, c3, c0, -c1, c3, -c2, c1, c0};
+        matmul<4, 4, 1>(L, b, q);
+        done.template put<0>();
+    }
+};
 
 // KalmanFilter.Prediction (ExtendedKalmanFilter.py:58-68), in two phases so that a batched
 // kernel needs R only once P^- is formed.  Phase 1: P^- = A P A^T + Jb Q Jb^T (:59-61).
@@ -141,44 +137,22 @@ __device__ __forceinline__ void d_predict_gain(const double *gyro, const double 
     matmul<4, 4, 4>(pm, Si, K);
 }
 
-__device__ __forceinline__ void d_predict(const double *gyro, const double *dt, const double *X,
-                                          const double *P, const double *Q, const double *R, double *z,
-                                          double *Pm, double *K, int32_t *status) {
-    d_predict_cov(gyro, X, P, Q, Pm);
-    d_predict_gain(gyro, dt, X, Pm, R, z, K, status);
-}
-
-__global__ __launch_bounds__(kBlock) void k_predict(int64_t n, const double *gyro,
-                                                   const double *dt, const double *X,
-                                                   const double *P, const double *Q,
-                                                   const double *R, double *z, double *Pm,
-                                                   double *K, int32_t *status, Done done) {
-    PEKF_TILE(t, 16, n);
-    // every operand's loads are issued up front (one memory round trip per wave)
-    double cg[3], cd[1], cx[4], cp[16], cq[9], cr[16], vg[3], vd[1], vx[4], vp[16], vq[9], vr[16];
-    t.gather(gyro, cg);
-    t.gather(dt, cd);
-    t.gather(X, cx);
-    t.gather(P, cp);
-    t.gather(Q, cq);
-    t.gather(R, cr);
-    t.to_lanes(cg, vg);
-    t.to_lanes(cd, vd);
-    t.to_lanes(cx, vx);
-    t.to_lanes(cp, vp);
-    t.to_lanes(cq, vq);
-    double opm[16];
-    d_predict_cov(vg, vx, vp, vq, opm);
-    t.store(Pm, opm);
-    t.to_lanes(cr, vr);
-    double oz[4], ok[16];
-    int32_t st = 0;
-    d_predict_gain(vg, vd, vx, opm, vr, oz, ok, &st);
-    t.store(z, oz);
-    t.store(K, ok);
-    if (status && t.active()) status[t.first + t.lane] = st;
-    done.signal();  // the whole block reaches this point (no early return)
-}
+struct OpPredict {
+    using In = Widths<3, 1, 4, 16, 9, 16>;  // gyro, dt, X, P, Q, R
+    using Out = Widths<4, 16, 16>;          // z, P^-, K
+    static constexpr int kErr = PEKF_ERR_SINGULAR;
+    static constexpr const char *kMsg = "Singular matrix", *kName = "k_predict";
+    template <class S>
+    __device__ __forceinline__ static void body(const double *gyro, const double *dt, const double *X,
+                                                const double *P, const double *Q, const double *R, double *z,
+                                                double *Pm, double *K, const S &done, int32_t *status) {
+        d_predict_cov(gyro, X, P, Q, Pm);
+        done.template put<1>();  // before the gain is formed
+        d_predict_gain(gyro, dt, X, Pm, R, z, K, status);
+        done.template put<0>();
+        done.template put<2>();
+    }
+};
 
 // KalmanFilter.Correction (ExtendedKalmanFilter.py:70-80), in parts so that a batched kernel
 // can form P - K P before the Wahba solve and keep only K live across it.  Phase 1: Y = Wahba(Acc, Mag, |Acc_z|,
@@ -219,157 +193,161 @@ __device__ __forceinline__ void d_correct_cov(const double *P, const double *K, 
     for (int k = 0; k < 16; ++k) Pout[k] = P[k] - kp[k];
 }
 
-__device__ __forceinline__ void d_correct(const double *mag, const double *acc, const double *z,
-                                          const double *P, const double *K, const double *acc0,
-                                          const double *mag0, double *X, double *Pout, int32_t *status) {
-    double y[4];
-    d_correct_measure(mag, acc, z, acc0, mag0, y, status);
-    d_correct_state(y, z, K, X);
-    d_correct_cov(P, K, Pout);
-}
-
-__global__ __launch_bounds__(kBlock) void k_correct(int64_t n, const double *mag,
-                                                   const double *acc, const double *z,
-                                                   const double *P, const double *K,
-                                                   const double *acc0, const double *mag0,
-                                                   double *X, double *Pout, int32_t *status, Done done) {
-    PEKF_TILE(t, 16, n);
-    // every operand's loads are issued up front (one memory round trip per wave); P - K P does
-    // not depend on the Wahba solve, so it is formed and stored first and only K stays live
-    double cp[16], ck[16], cm[3], ca[3], cz[4], cm0[3], ca0[3];
-    t.gather(P, cp);
-    t.gather(K, ck);
-    t.gather(mag, cm);
-    t.gather(acc, ca);
-    t.gather(z, cz);
-    t.gather(acc0, ca0);
-    t.gather(mag0, cm0);
-    double vp[16], vk[16], op[16];
-    t.to_lanes(cp, vp);
-    t.to_lanes(ck, vk);
-    d_correct_cov(vp, vk, op);
-    t.store(Pout, op);
-    double vm[3], va[3], vz[4], vm0[3], va0[3], y[4], ox[4];
-    t.to_lanes(cm, vm);
-    t.to_lanes(ca, va);
-    t.to_lanes(cz, vz);
-    t.to_lanes(ca0, va0);
-    t.to_lanes(cm0, vm0);
-    int32_t st = 0;
-    d_correct_measure(vm, va, vz, va0, vm0, y, &st);
-    d_correct_state(y, vz, vk, ox);
-    t.store(X, ox);
-    if (status && t.active()) status[t.first + t.lane] = st;
-    done.signal();  // the whole block reaches this point (no early return)
-}
-
-template <bool QUAT>
-__device__ __forceinline__ void d_wahba(int64_t i, const double *acc0,
-                                                 const double *mag0, const double *acc,
-                                                 const double *mag, const double *ka,
-                                                 const double *km, double *out, int32_t *status) {
-    if (status)
-        status[i] = wahba_b_finite(acc0 + 3 * i, mag0 + 3 * i, acc + 3 * i, mag + 3 * i, ka[i], km[i]) ? 0 : 1;
-    double R[9];
-    wahba_rotation_vectors(acc0 + 3 * i, mag0 + 3 * i, acc + 3 * i, mag + 3 * i, ka[i], km[i], R);
-    if (QUAT) {
-        rotm_to_quat(R, out + 4 * i);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) out[9 * i + k] = R[k];
+struct OpCorrect {
+    using In = Widths<3, 3, 4, 16, 16, 3, 3>;  // mag, acc, z, P, K, acc0, mag0
+    using Out = Widths<4, 16>;                 // X, P
+    static constexpr int kErr = PEKF_ERR_SVD;
+    static constexpr const char *kMsg = "SVD did not converge", *kName = "k_correct";
+    template <class S>
+    __device__ __forceinline__ static void body(const double *mag, const double *acc, const double *z,
+                                                const double *P, const double *K, const double *acc0,
+                                                const double *mag0, double *X, double *Pout, const S &done,
+                                                int32_t *status) {
+        double y[4];
+        d_correct_cov(P, K, Pout);
+        done.template put<1>();  // first: only K stays live across the Wahba solve
+        d_correct_measure(mag, acc, z, acc0, mag0, y, status);
+        d_correct_state(y, z, K, X);
+        done.template put<0>();
     }
-}
+};
 
+// Wahba's rotation from two vector pairs, as a quaternion or as the matrix; status 1 = non-finite B
 template <bool QUAT>
-__global__ __launch_bounds__(kBlock) void k_wahba(int64_t n, const double *acc0,
-                                                 const double *mag0, const double *acc,
-                                                 const double *mag, const double *ka,
-                                                 const double *km, double *out, int32_t *status, Done done) {
-    PEKF_TILE(t, 9, n);
-    double c0[3], c1[3], c2[3], c3[3], c4[1], c5[1], v0[3], v1[3], v2[3], v3[3], v4[1], v5[1];
-    t.gather(acc0, c0);
-    t.gather(mag0, c1);
-    t.gather(acc, c2);
-    t.gather(mag, c3);
-    t.gather(ka, c4);
-    t.gather(km, c5);
-    t.to_lanes(c0, v0);
-    t.to_lanes(c1, v1);
-    t.to_lanes(c2, v2);
-    t.to_lanes(c3, v3);
-    t.to_lanes(c4, v4);
-    t.to_lanes(c5, v5);
-    double o[QUAT ? 4 : 9];
+struct OpWahba {
+    using In = Widths<3, 3, 3, 3, 1, 1>;  // acc0, mag0, acc, mag, k_acc, k_mag
+    using Out = Widths<QUAT ? 4 : 9>;
+    static constexpr int kErr = PEKF_ERR_SVD;
+    static constexpr const char *kMsg = "SVD did not converge", *kName = "k_wahba";
+    template <class S>
+    __device__ __forceinline__ static void body(const double *acc0, const double *mag0, const double *acc,
+                                                const double *mag, const double *ka, const double *km,
+                                                double *out, const S &done, int32_t *status) {
+        double R[9];
+        wahba_rotation_vectors(acc0, mag0, acc, mag, ka[0], km[0], R);
+        // after the solve: formed beside it, the check's operands lengthen the solve's live ranges
+        *status = wahba_b_finite(acc0, mag0, acc, mag, ka[0], km[0]) ? 0 : 1;
+        if constexpr (QUAT) {
+            rotm_to_quat(R, out);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) out[k] = R[k];
+        }
+        done.template put<0>();
+    }
+};
+
+struct OpR2q {
+    using In = Widths<9>;  // M
+    using Out = Widths<4>;
+    static constexpr int kErr = PEKF_OK;
+    static constexpr const char *kMsg = nullptr, *kName = "k_r2q";
+    template <class S>
+    __device__ __forceinline__ static void body(const double *M, double *q, const S &done, int32_t *) {
+        rotm_to_quat(M, q);
+        done.template put<0>();
+    }
+};
+
+template <int W>
+__device__ __forceinline__ double (&span(double *p))[W] {
+    return *reinterpret_cast<double(*)[W]>(p);
+}
+
+// Sinks of a body: output K, complete in an item's lane-private outputs o, goes to its plane as a tile
+// store; or, where the body wrote to the destination itself, nothing is left to do
+template <class Op>
+struct TileSink {
+    const WaveTile &t;
+    double *const *plane;
+    double *o;
+    template <int K>
+    __device__ __forceinline__ void put() const {
+        t.store(plane[K], span<Op::Out::w(K)>(o + Op::Out::off(K)));
+    }
+};
+struct InPlace {
+    template <int K>
+    __device__ __forceinline__ void put() const {}
+};
+
+// The batched kernel: every operand's loads are issued up front (one memory round trip per wave), then
+// transposed to lanes; the body stores each output as it completes.
+template <class Op, size_t... I, size_t... O>
+__device__ __forceinline__ void op_tile(const WaveTile &t, const OpPtrs<Op> &p, int32_t *status,
+                                        std::index_sequence<I...>, std::index_sequence<O...>) {
+    using In = typename Op::In;
+    double c[In::total], v[In::total], o[Op::Out::total];
+    (t.gather(p.in[I], span<In::w(I)>(c + In::off(I))), ...);
+    (t.to_lanes(span<In::w(I)>(c + In::off(I)), span<In::w(I)>(v + In::off(I))), ...);
     int32_t st = 0;
-    d_wahba<QUAT>(0, v0, v1, v2, v3, v4, v5, o, &st);
-    t.store(out, o);
-    if (status && t.active()) status[t.first + t.lane] = st;
-    done.signal();  // the whole block reaches this point (no early return)
+    Op::body(v + In::off(I)..., o + Op::Out::off(O)..., TileSink<Op>{t, p.out, o}, &st);
+    if constexpr (Op::kErr != PEKF_OK)
+        if (status && t.active()) status[t.first + t.lane] = st;
 }
 
-__device__ __forceinline__ void d_r2q(int64_t i, const double *M, double *q) {
-    rotm_to_quat(M + 9 * i, q + 4 * i);
-}
-
-__global__ __launch_bounds__(kBlock) void k_r2q(int64_t n, const double *M, double *q, Done done) {
-    PEKF_TILE(t, 9, n);
-    double vm[9], o[4];
-    t.load(M, vm);
-    d_r2q(0, vm, o);
-    t.store(q, o);
+template <class Op>
+__global__ __launch_bounds__(kBlock) void k_op(int64_t n, OpPtrs<Op> p, int32_t *status, Done done) {
+    // LDS for the WaveTiles of a block, sized by the operator's widest operand
+    constexpr int kSlice = tile_doubles<std::max(Op::In::widest, Op::Out::widest)>();
+    __shared__ double pool[kBlock / kWave * kSlice];
+    op_tile<Op>(WaveTile(pool, kSlice, n), p, status, std::make_index_sequence<Op::In::count>{},
+                std::make_index_sequence<Op::Out::count>{});
     done.signal();  // the whole block reaches this point (no early return)
 }
 
 // n = 1 calls (what main_file.py makes, one record at a time): the inputs travel by value in the
 // kernel-argument segment with the dispatch itself instead of being read over PCIe from pinned
-// host memory, so the kernel starts with its operands in hand.  The body is the same device
-// function as the batched kernel, on a private copy (promoted to registers after inlining).
+// host memory, so the kernel starts with its operands in hand.  The body is the table's, on a
+// private copy (promoted to registers after inlining).
 constexpr int kBlobDoubles = 64;
 struct Blob {
     double v[kBlobDoubles];
 };
-enum : int {
-    kCallPredict = 0,    // gyro 3, dt 1, X 4, P 16, Q 9, R 16 -> z 4, Pm 16, K 16
-    kCallCorrect = 1,    // mag 3, acc 3, z 4, P 16, K 16, acc0 3, mag0 3 -> X 4, P 16
-    kCallWahbaQuat = 2,  // acc0 3, mag0 3, acc 3, mag 3, ka 1, km 1 -> q 4
-    kCallWahbaRot = 3,   // as above -> R 9
-    kCallRk4 = 4,        // q0 4, dt 1, w 3 -> q 4
-    kCallJacA = 5,       // w 3 -> A 16
-    kCallJacB = 6,       // q 4 -> Jb 12
-    kCallComparator = 7, // q1 4, q2 4 -> 4
-    kCallR2q = 8,        // M 9 -> q 4
-};
-constexpr int kCallMaxOut = 36;
 
-__host__ __device__ constexpr int call1_outputs(int op) {
-    return op == kCallPredict ? 36 : op == kCallCorrect ? 20 : op == kCallWahbaRot ? 9 : op == kCallJacA ? 16
-           : op == kCallJacB ? 12 : 4;
+template <class Op, size_t... I, size_t... O>
+__device__ __forceinline__ void run1(const double *v, double *o, int32_t *st, std::index_sequence<I...>,
+                                     std::index_sequence<O...>) {
+    Op::body(v + Op::In::off(I)..., o + Op::Out::off(O)..., InPlace{}, st);
+}
+template <class Op>
+__device__ __forceinline__ void run1(const double *v, double *o, int32_t *st) {
+    run1<Op>(v, o, st, std::make_index_sequence<Op::In::count>{}, std::make_index_sequence<Op::Out::count>{});
 }
 
-// One n = 1 call on lane-private operands (the operand order above); status stays 0 for the
-// operators that cannot fail.
-__device__ __forceinline__ void dispatch1(int op, const double *v, double *o, int32_t *st) {
-    switch (op) {
-        case kCallPredict: d_predict(v, v + 3, v + 4, v + 8, v + 24, v + 33, o, o + 4, o + 20, st); break;
-        case kCallCorrect: d_correct(v, v + 3, v + 6, v + 10, v + 26, v + 42, v + 45, o, o + 4, st); break;
-        case kCallWahbaQuat: d_wahba<true>(0, v, v + 3, v + 6, v + 9, v + 12, v + 13, o, st); break;
-        case kCallWahbaRot: d_wahba<false>(0, v, v + 3, v + 6, v + 9, v + 12, v + 13, o, st); break;
-        case kCallRk4: d_rk4(0, v, v + 4, v + 5, o); break;
-        case kCallJacA: d_jac_a(0, v, o); break;
-        case kCallJacB: d_jac_b(0, v, o); break;
-        case kCallComparator: d_comparator(0, v, v + 4, o); break;
-        default: d_r2q(0, v, o); break;
+// The table itself: an operator's position is its code in a service request.
+template <class... Op>
+struct OpList {
+    static constexpr int kMaxIn = std::max({Op::In::total...}), kMaxOut = std::max({Op::Out::total...});
+    template <class T>
+    static constexpr int code() {
+        int k = 0, at = -1;
+        ((std::is_same_v<T, Op> ? at = k++ : k++), ...);
+        return at;
     }
-}
+    static constexpr int outputs(int op) {  // doubles an operator returns
+        int k = 0, n = 0;
+        ((op == k++ ? n = Op::Out::total : 0), ...);
+        return n;
+    }
+    // the operator `op` on lane-private operands, its outputs at their offsets in o
+    __device__ __forceinline__ static void run(int op, const double *v, double *o, int32_t *st) {
+        int k = 0;
+        ((op == k++ ? run1<Op>(v, o, st) : void()), ...);
+    }
+};
+using Ops = OpList<OpPredict, OpCorrect, OpWahba<true>, OpWahba<false>, OpRk4, OpJacA, OpJacB, OpComparator, OpR2q>;
+constexpr int kCallMaxOut = Ops::kMaxOut;  // the widest operator's outputs
+static_assert(Ops::kMaxIn <= kBlobDoubles, "every operator's inputs fit the Blob");
 
-template <int OP>
+template <class Op>
 __global__ __launch_bounds__(64) void k_call1(Blob b, double *out, int32_t *status, Done done) {
     if (threadIdx.x == 0) {
         double v[kBlobDoubles];
 #pragma unroll
         for (int k = 0; k < kBlobDoubles; ++k) v[k] = b.v[k];
-        *status = 0;
-        dispatch1(OP, v, out, status);
+        *status = 0;  // stays 0 for the operators that cannot fail
+        run1<Op>(v, out, status);
     }
     done.signal();
 }
@@ -391,7 +369,10 @@ __global__ __launch_bounds__(64) void k_call1(Blob b, double *out, int32_t *stat
 // stops calling leaves nothing running for more than kSvcIdleMs.
 constexpr int kSvcLinePayload = 7;
 constexpr int kSvcPayload = 8 * kSvcLinePayload;  // 56 doubles
-constexpr size_t kSvcRespOff = 1024, kSvcStatusOff = kSvcRespOff + 64 * 8, kSvcSeqOff = kSvcStatusOff + 64;
+constexpr int kSvcRespDoubles = 64;
+constexpr size_t kSvcRespOff = 1024, kSvcStatusOff = kSvcRespOff + kSvcRespDoubles * 8, kSvcSeqOff = kSvcStatusOff + 64;
+static_assert(Ops::kMaxIn <= kSvcPayload, "every operator's inputs fit a request");
+static_assert(kCallMaxOut <= kSvcRespDoubles, "every operator's outputs fit the response area");
 constexpr size_t kSvcBytes = 2048;
 constexpr uint32_t kSvcStop = 0xFFFFu;
 constexpr int kSvcIdleMs = 5;
@@ -415,7 +396,7 @@ __device__ inline uint32_t xor8(uint32_t h) {
 // The request's operation on lane 0, out of line so that the polling loop carries none of its
 // hoisted constants (inlined, they were copied through AGPRs on every poll).
 __device__ __noinline__ void svc_run(uint32_t op, double *sh, int32_t *sh_status) {
-    // the payload as the Blob of k_call1 (same operand order, same device functions)
+    // the payload as the Blob of k_call1 (same operand order, same bodies)
     double v[kSvcPayload];
 #pragma unroll
     for (int k = 0; k < 8; ++k)
@@ -423,7 +404,7 @@ __device__ __noinline__ void svc_run(uint32_t op, double *sh, int32_t *sh_status
         for (int j = 0; j < kSvcLinePayload; ++j) v[k * kSvcLinePayload + j] = sh[k * 8 + j];
     double o[kCallMaxOut] = {};
     int32_t st = 0;
-    dispatch1((int)op, v, o, &st);
+    Ops::run((int)op, v, o, &st);
 #pragma unroll
     for (int k = 0; k < kCallMaxOut; ++k) sh[k] = o[k];  // static indices: o stays in registers
     *sh_status = st;
@@ -455,17 +436,18 @@ __device__ __forceinline__ constexpr int svc_at(int k) { return (k / kSvcLinePay
 
 __device__ __noinline__ void svc_predict_wave(double *sh, double *sx, int32_t *sh_status) {
     const int lane = threadIdx.x, l = lane & 15, i = l >> 2, j = l & 3;
-    // operands (d_predict's order: gyro 3, dt 1, X 4, P 16, Q 9, R 16)
+    using In = OpPredict::In;  // gyro, dt, X, P, Q, R
+    using Out = OpPredict::Out;
     double g[3], dt, x[4];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) g[k] = sh[svc_at(k)];
-    dt = sh[svc_at(3)];
+    for (int k = 0; k < 3; ++k) g[k] = sh[svc_at(In::off(0) + k)];
+    dt = sh[svc_at(In::off(1))];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) x[k] = sh[svc_at(4 + k)];
+    for (int k = 0; k < 4; ++k) x[k] = sh[svc_at(In::off(2) + k)];
     double *A = sx, *Jb = sx + 16, *P = sx + 28, *Q = sx + 44, *T = sx + 53, *T12 = sx + 69, *Si = sx + 81;
-    if (lane < 16) P[l] = sh[svc_at(8 + l)];
-    if (lane < 9) Q[lane] = sh[svc_at(24 + lane)];
-    const double R = sh[svc_at(33 + l)];
+    if (lane < 16) P[l] = sh[svc_at(In::off(3) + l)];
+    if (lane < 9) Q[lane] = sh[svc_at(In::off(4) + lane)];
+    const double R = sh[svc_at(In::off(5) + l)];
     if (lane == 0) {
         double a[16], jb[12];
         omega_half(g, a);
@@ -506,32 +488,33 @@ __device__ __noinline__ void svc_predict_wave(double *sh, double *sx, int32_t *s
     __syncthreads();
     const double kk = ok ? dot_row_col(P + 4 * i, 1, Si + j, 4, 4) : NAN;
     __syncthreads();
-    // outputs in the order of call1_outputs: z 4, Pm 16, K 16
-    if (lane < 4) sh[lane] = pick4(z, lane);
+    // outputs: z, P^-, K
+    if (lane < 4) sh[Out::off(0) + lane] = pick4(z, lane);
     if (lane < 16) {
-        sh[4 + l] = pm;
-        sh[20 + l] = kk;
+        sh[Out::off(1) + l] = pm;
+        sh[Out::off(2) + l] = kk;
     }
     if (lane == 0) *sh_status = ok ? 0 : 1;
 }
 
 __device__ __noinline__ void svc_correct_wave(double *sh, double *sx, int32_t *sh_status) {
     const int lane = threadIdx.x, l = lane & 15, i = l >> 2, j = l & 3;
-    // operands (d_correct's order: mag 3, acc 3, z 4, P 16, K 16, acc0 3, mag0 3)
+    using In = OpCorrect::In;  // mag, acc, z, P, K, acc0, mag0
+    using Out = OpCorrect::Out;
     double mag[3], acc[3], z[4], a0[3], m0[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        mag[k] = sh[svc_at(k)];
-        acc[k] = sh[svc_at(3 + k)];
-        a0[k] = sh[svc_at(42 + k)];
-        m0[k] = sh[svc_at(45 + k)];
+        mag[k] = sh[svc_at(In::off(0) + k)];
+        acc[k] = sh[svc_at(In::off(1) + k)];
+        a0[k] = sh[svc_at(In::off(5) + k)];
+        m0[k] = sh[svc_at(In::off(6) + k)];
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) z[k] = sh[svc_at(6 + k)];
+    for (int k = 0; k < 4; ++k) z[k] = sh[svc_at(In::off(2) + k)];
     double *P = sx, *K = sx + 16;
     if (lane < 16) {
-        P[l] = sh[svc_at(10 + l)];
-        K[l] = sh[svc_at(26 + l)];
+        P[l] = sh[svc_at(In::off(3) + l)];
+        K[l] = sh[svc_at(In::off(4) + l)];
     }
     __syncthreads();
     // d_correct_cov: P - K P, one entry per lane
@@ -544,9 +527,9 @@ __device__ __noinline__ void svc_correct_wave(double *sh, double *sx, int32_t *s
     for (int k = 0; k < 16; ++k) kr[k] = K[k];
     d_correct_state(y, z, kr, X);
     __syncthreads();
-    // outputs: X 4, P 16
-    if (lane < 4) sh[lane] = pick4(X, lane);
-    if (lane < 16) sh[4 + l] = pout;
+    // outputs: X, P
+    if (lane < 4) sh[Out::off(0) + lane] = pick4(X, lane);
+    if (lane < 16) sh[Out::off(1) + l] = pout;
     if (lane == 0) *sh_status = st;
 }
 
@@ -587,10 +570,10 @@ __global__ __launch_bounds__(64) void k_service(char *box, unsigned long long id
         }
         sh[lane] = __longlong_as_double((long long)w);
         __syncthreads();
-        const int n_out = call1_outputs((int)op);
-        if (op == kCallPredict)
+        const int n_out = Ops::outputs((int)op);
+        if (op == Ops::code<OpPredict>())
             svc_predict_wave(sh, sx, &sh_status);  // op is wave-uniform: every lane takes part
-        else if (op == kCallCorrect)
+        else if (op == Ops::code<OpCorrect>())
             svc_correct_wave(sh, sx, &sh_status);
         else if (lane == 0)
             svc_run(op, sh, &sh_status);
@@ -775,42 +758,59 @@ void service_quiesce_all() { Service::quiesce_all(); }
 
 // Host side of k_call1: packs the inputs (in order) into the Blob, runs the call with zero-copy
 // outputs and returns them (in order) plus the status word.
-template <int OP>
-static int call1(std::initializer_list<HostArg> ins, std::initializer_list<HostOut> outs, int32_t *status) {
+template <class Op>
+static int call1(const OpPtrs<Op> &a, int32_t *status) {
+    using In = typename Op::In;
+    using Out = typename Op::Out;
     Blob b;
-    size_t off = 0;
-    for (const HostArg &a : ins) {
-        std::memcpy(reinterpret_cast<char *>(b.v) + off, a.ptr, a.bytes);
-        off += a.bytes;
-    }
-    size_t ob = 0;
-    for (const HostOut &o : outs) ob += o.bytes;
+    for (int k = 0; k < In::count; ++k) std::memcpy(b.v + In::off(k), a.in[k], In::w(k) * sizeof(double));
     double tmp[kBlobDoubles];
-    // the resident service when it is available, a launch of k_call1 otherwise (same d_* bodies)
-    Service *svc = off <= kSvcPayload * sizeof(double) ? Service::get() : nullptr;
-    if (svc) {
-        if (svc->call(OP, b.v, off / sizeof(double), tmp, (int)(ob / sizeof(double)), status) == PEKF_OK) {
-            off = 0;
-            for (const HostOut &o : outs) {
-                std::memcpy(o.ptr, reinterpret_cast<char *>(tmp) + off, o.bytes);
-                off += o.bytes;
-            }
-            return PEKF_OK;
-        }
-    }
+    auto deliver = [&] {
+        for (int k = 0; k < Out::count; ++k) std::memcpy(a.out[k], tmp + Out::off(k), Out::w(k) * sizeof(double));
+        return PEKF_OK;
+    };
+    // the resident service when it is available, a launch of k_call1 otherwise (same bodies)
+    Service *svc = Service::get();
+    if (svc && svc->call(Ops::code<Op>(), b.v, In::total, tmp, Out::total, status) == PEKF_OK) return deliver();
     Staging &s = Staging::get();
+    constexpr size_t ob = Out::total * sizeof(double);
     void *out[2];
     if (int st = s.stage_in({}, {ob, sizeof(int32_t)}, nullptr, out)) return st;
-    hipLaunchKernelGGL(k_call1<OP>, dim3(1), dim3(64), 0, s.stream(), b, static_cast<double *>(out[0]),
+    hipLaunchKernelGGL(k_call1<Op>, dim3(1), dim3(64), 0, s.stream(), b, static_cast<double *>(out[0]),
                        static_cast<int32_t *>(out[1]), s.done(1));
     if (int st = launched("k_call1")) return st;
     if (int st = s.stage_out({{tmp, ob}, {status, sizeof(int32_t)}}, out)) return st;
-    off = 0;
-    for (const HostOut &o : outs) {
-        std::memcpy(o.ptr, reinterpret_cast<char *>(tmp) + off, o.bytes);
-        off += o.bytes;
-    }
+    return deliver();
+}
+
+// The checks of every entry point of a table operator, over exactly its operands (an empty batch passes:
+// the caller returns before touching a pointer).
+template <class Op>
+static int op_args(int64_t n, const OpPtrs<Op> &a) {
+    PEKF_CHECK_ARG(n >= 0, "n < 0");
+    bool null = false;
+    for (const double *p : a.in) null |= !p;
+    for (const double *p : a.out) null |= !p;
+    PEKF_CHECK_ARG(n == 0 || !null, "null pointer");
     return PEKF_OK;
+}
+
+// The host-pointer route: staged operands, the n = 1 route for one item, the status plane mapped to the
+// operator's error.
+template <class Op>
+static int host_op(int64_t n, const OpPtrs<Op> &a) {
+    if (int st = op_args(n, a)) return st;
+    if (n == 0) return PEKF_OK;
+    return staged_call<Op, kBlock, call1<Op>>(k_op<Op>, n, a);
+}
+
+// The device-pointer route: the launch alone, on the caller's stream; status may be NULL.
+template <class Op>
+static int dev_op(int64_t n, const OpPtrs<Op> &a, int32_t *status, void *stream) {
+    if (int st = op_args(n, a)) return st;
+    if (n == 0) return PEKF_OK;
+    hipLaunchKernelGGL(k_op<Op>, PEKF_GRID(n), 0, as_stream(stream), n, a, status, kNoSignal);
+    return launched(Op::kName);
 }
 
 }  // namespace pekf
@@ -832,46 +832,27 @@ int pekf_get_percall_mode(int *mode) {
     return PEKF_OK;
 }
 
-// ------------------------------- device-pointer variants -------------------------------------
+// Every operator entry below states its pointers in ABI order; widths, checks and routes come from the table.
 
 int pekf_rk4_dev(int64_t n, const double *q0, const double *dt_ns, const double *w, double *q_out,
                  void *stream) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(q0 && dt_ns && w && q_out, "null pointer");
-    hipLaunchKernelGGL(k_rk4, PEKF_GRID(n), 0, as_stream(stream), n, q0, dt_ns, w, q_out, kNoSignal);
-    return launched("k_rk4");
+    return dev_op<OpRk4>(n, {{q0, dt_ns, w}, {q_out}}, nullptr, stream);
 }
 
 int pekf_predict_dev(int64_t n, const double *gyro, const double *dt_ns, const double *X,
                      const double *P, const double *Q, const double *R, double *z, double *Pm,
                      double *K, int32_t *status, void *stream) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(gyro && dt_ns && X && P && Q && R && z && Pm && K, "null pointer");
-    hipLaunchKernelGGL(k_predict, PEKF_GRID(n), 0, as_stream(stream), n, gyro, dt_ns, X, P, Q, R,
-                       z, Pm, K, status, kNoSignal);
-    return launched("k_predict");
+    return dev_op<OpPredict>(n, {{gyro, dt_ns, X, P, Q, R}, {z, Pm, K}}, status, stream);
 }
 
 int pekf_correct_dev(int64_t n, const double *mag, const double *acc, const double *z,
                      const double *P, const double *K, const double *acc0, const double *mag0,
                      double *X, double *P_out, void *stream) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(mag && acc && z && P && K && acc0 && mag0 && X && P_out, "null pointer");
-    hipLaunchKernelGGL(k_correct, PEKF_GRID(n), 0, as_stream(stream), n, mag, acc, z, P, K, acc0,
-                       mag0, X, P_out, nullptr, kNoSignal);
-    return launched("k_correct");
+    return dev_op<OpCorrect>(n, {{mag, acc, z, P, K, acc0, mag0}, {X, P_out}}, nullptr, stream);
 }
 
-// ------------------------------- host-pointer variants ---------------------------------------
-
 int pekf_rk4(int64_t n, const double *q0, const double *dt_ns, const double *w, double *q_out) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(q0 && dt_ns && w && q_out, "null pointer");
-    return staged_call<kBlock, call1<kCallRk4>>(k_rk4, "k_rk4", n, {{q0, 4}, {dt_ns, 1}, {w, 3}}, {{q_out, 4}});
+    return host_op<OpRk4>(n, {{q0, dt_ns, w}, {q_out}});
 }
 
 // written out: k_norm takes len as well, and has no n = 1 route
@@ -890,78 +871,36 @@ int pekf_norm(int64_t n, int64_t len, const double *a, double *res) {
     return s.stage_out({{res, b}}, out);
 }
 
-int pekf_jacobian_a(int64_t n, const double *w, double *A) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(w && A, "null pointer");
-    return staged_call<kBlock, call1<kCallJacA>>(k_jac_a, "k_jac_a", n, {{w, 3}}, {{A, 16}});
-}
+int pekf_jacobian_a(int64_t n, const double *w, double *A) { return host_op<OpJacA>(n, {{w}, {A}}); }
 
-int pekf_jacobian_b(int64_t n, const double *q, double *Jb) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(q && Jb, "null pointer");
-    return staged_call<kBlock, call1<kCallJacB>>(k_jac_b, "k_jac_b", n, {{q, 4}}, {{Jb, 12}});
-}
+int pekf_jacobian_b(int64_t n, const double *q, double *Jb) { return host_op<OpJacB>(n, {{q}, {Jb}}); }
 
 int pekf_comparator(int64_t n, const double *q1, const double *q2, double *res) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(q1 && q2 && res, "null pointer");
-    return staged_call<kBlock, call1<kCallComparator>>(k_comparator, "k_comparator", n, {{q1, 4}, {q2, 4}},
-                                                       {{res, 4}});
+    return host_op<OpComparator>(n, {{q1, q2}, {res}});
 }
 
 int pekf_predict(int64_t n, const double *gyro, const double *dt_ns, const double *X,
                  const double *P, const double *Q, const double *R, double *z, double *Pm,
                  double *K) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(gyro && dt_ns && X && P && Q && R && z && Pm && K, "null pointer");
-    return staged_call<kBlock, call1<kCallPredict>, PEKF_ERR_SINGULAR>(
-        k_predict, "k_predict", n, {{gyro, 3}, {dt_ns, 1}, {X, 4}, {P, 16}, {Q, 9}, {R, 16}},
-        {{z, 4}, {Pm, 16}, {K, 16}}, "Singular matrix");
+    return host_op<OpPredict>(n, {{gyro, dt_ns, X, P, Q, R}, {z, Pm, K}});
 }
 
 int pekf_correct(int64_t n, const double *mag, const double *acc, const double *z,
                  const double *P, const double *K, const double *acc0, const double *mag0,
                  double *X, double *P_out) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(mag && acc && z && P && K && acc0 && mag0 && X && P_out, "null pointer");
-    return staged_call<kBlock, call1<kCallCorrect>, PEKF_ERR_SVD>(
-        k_correct, "k_correct", n, {{mag, 3}, {acc, 3}, {z, 4}, {P, 16}, {K, 16}, {acc0, 3}, {mag0, 3}},
-        {{X, 4}, {P_out, 16}}, "SVD did not converge");
-}
-
-static int wahba_host(bool quat, int64_t n, const double *acc0, const double *mag0,
-                      const double *acc, const double *mag, const double *k_acc,
-                      const double *k_mag, double *res) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(acc0 && mag0 && acc && mag && k_acc && k_mag && res, "null pointer");
-    const OpIn ins[] = {{acc0, 3}, {mag0, 3}, {acc, 3}, {mag, 3}, {k_acc, 1}, {k_mag, 1}};
-    constexpr Call1Fn one_quat = call1<kCallWahbaQuat>, one_rot = call1<kCallWahbaRot>;
-    const char *err = "SVD did not converge";
-    if (quat) return staged_call<kBlock, one_quat, PEKF_ERR_SVD>(k_wahba<true>, "k_wahba", n, ins, {{res, 4}}, err);
-    return staged_call<kBlock, one_rot, PEKF_ERR_SVD>(k_wahba<false>, "k_wahba", n, ins, {{res, 9}}, err);
+    return host_op<OpCorrect>(n, {{mag, acc, z, P, K, acc0, mag0}, {X, P_out}});
 }
 
 int pekf_wahba_rotation(int64_t n, const double *acc0, const double *mag0, const double *acc,
                         const double *mag, const double *k_acc, const double *k_mag, double *R) {
-    return wahba_host(false, n, acc0, mag0, acc, mag, k_acc, k_mag, R);
+    return host_op<OpWahba<false>>(n, {{acc0, mag0, acc, mag, k_acc, k_mag}, {R}});
 }
 
 int pekf_wahba_quaternion(int64_t n, const double *acc0, const double *mag0, const double *acc,
                           const double *mag, const double *k_acc, const double *k_mag, double *q) {
-    return wahba_host(true, n, acc0, mag0, acc, mag, k_acc, k_mag, q);
+    return host_op<OpWahba<true>>(n, {{acc0, mag0, acc, mag, k_acc, k_mag}, {q}});
 }
 
-int pekf_rotmat_to_quat(int64_t n, const double *M, double *q) {
-    PEKF_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(M && q, "null pointer");
-    return staged_call<kBlock, call1<kCallR2q>>(k_r2q, "k_r2q", n, {{M, 9}}, {{q, 4}});
-}
+int pekf_rotmat_to_quat(int64_t n, const double *M, double *q) { return host_op<OpR2q>(n, {{M}, {q}}); }
 
 }  // extern "C"

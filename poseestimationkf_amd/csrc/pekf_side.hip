@@ -198,10 +198,17 @@ __device__ __forceinline__ void d_rpy(int64_t i, const double *__restrict__ q, d
     rpy[3 * i + 2] = atan2(siny, cosy) * k;
 }
 
-__global__ __launch_bounds__(kSideBlock) void k_rpy(int64_t n, const double *__restrict__ q,
-                                                    double *__restrict__ rpy, Done done) {
+// its entry in the form of the per-call operator table (pekf_percall.hip): no status plane, no n = 1 route
+struct OpRpy {
+    using In = Widths<4>;   // q
+    using Out = Widths<3>;  // roll, pitch, yaw
+    static constexpr int kErr = PEKF_OK;
+    static constexpr const char *kMsg = nullptr, *kName = "k_rpy";
+};
+
+__global__ __launch_bounds__(kSideBlock) void k_rpy(int64_t n, OpPtrs<OpRpy> p, int32_t *, Done done) {
     const int64_t i = (int64_t)blockIdx.x * kSideBlock + threadIdx.x;
-    if (i < n) d_rpy(i, q, rpy);
+    if (i < n) d_rpy(i, p.in[0], p.out[0]);
     done.signal();
 }
 
@@ -288,7 +295,7 @@ int pekf_quat_to_rpy_dev(int64_t n, const double *q, double *rpy, void *stream) 
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(q && rpy, "null pointer");
     hipLaunchKernelGGL(k_rpy, dim3(grid_for(n, kSideBlock)), dim3(kSideBlock), 0, as_stream(stream), n,
-                       q, rpy, kNoSignal);
+                       OpPtrs<OpRpy>{{q}, {rpy}}, nullptr, kNoSignal);
     return launched("k_rpy");
 }
 
@@ -296,7 +303,7 @@ int pekf_quat_to_rpy(int64_t n, const double *q, double *rpy) {
     PEKF_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return PEKF_OK;
     PEKF_CHECK_ARG(q && rpy, "null pointer");
-    return staged_call<kSideBlock>(k_rpy, "k_rpy", n, {{q, 4}}, {{rpy, 3}});  // no n = 1 route
+    return staged_call<OpRpy, kSideBlock>(k_rpy, n, {{q}, {rpy}});
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 eps), methods and return tuples, so ``main_file.py`` runs unchanged against it.  X, P, z
 and K are caller-owned values: every call returns fresh arrays and never mutates its
 inputs (main_file.py:39-44 keeps the returned X in a list).  The arithmetic runs in the
-per-call gfx950 kernels of libpekf.so (k_predict, k_correct, k_rk4, ...); the two per-record
+per-call gfx950 kernels of libpekf.so (k_op<OpPredict>, k_op<OpCorrect>, k_op<OpRk4>, ...); the two per-record
 methods go through the CPython binding ``_fastcall`` (same C entry points, less call overhead).  For many
 filters at once use ``poseestimationkf_amd.engine.BatchedEKF`` (the fused kernel).
 ``predict`` / ``update`` are aliases of ``Prediction`` / ``Correction`` (the north_star's names).

@@ -1,7 +1,7 @@
 """Drop-in for the reference module ``Wahba`` (Python Kalman Filter/Wahba.py).
 
 Same class, attribute and method names and return types; every computation runs in the
-gfx950 kernels of libpekf.so (k_wahba, k_r2q) through the C ABI.  The SVD of the rank-2
+gfx950 kernels of libpekf.so (k_op<OpWahba>, k_op<OpR2q>) through the C ABI.  The SVD of the rank-2
 attitude profile matrix is replaced by its closed form (DESIGN.md "Wahba closed form");
 the rotation is unique, so results agree with np.linalg.svd to rounding.  ``solve`` is an alias
 of ``getQuarternion`` (the north_star's name).

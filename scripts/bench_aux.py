@@ -123,6 +123,34 @@ def c1_loop():
     return out
 
 
+def percall_dev(s):
+    """The per-call predict / correct kernels at n = 1M items on device pointers (stream s): what an A/B of
+    two builds alternates (PEKF_LIB selects the build)."""
+    res = {}
+    n = 1 << 20
+    rng = np.random.default_rng(0)
+    X = rng.normal(size=(n, 4))
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    bufs = {k: engine.DeviceBuffer(a.nbytes).upload(np.ascontiguousarray(a)) for k, a in dict(
+        g=rng.normal(size=(n, 3)), dt=np.full(n, 1e7), X=X, P=np.tile(np.eye(4), (n, 1, 1)),
+        Q=np.tile(np.eye(3), (n, 1, 1)), R=np.tile(np.eye(4) * 0.1, (n, 1, 1)), acc=X[:, :3].copy(),
+        mag=X[:, 1:].copy(), a0=np.tile([0, 0, 1.0], (n, 1)), m0=np.tile([0.5, 0, -0.86], (n, 1))).items()}
+    z, Pm, Kk, Xo, Po = (engine.DeviceBuffer(8 * n * k) for k in (4, 16, 16, 4, 16))
+    b = bufs
+    ms = timed(lambda: check(lib.pekf_predict_dev(n, b["g"].ptr, b["dt"].ptr, b["X"].ptr, b["P"].ptr, b["Q"].ptr,
+                                                  b["R"].ptr, z.ptr, Pm.ptr, Kk.ptr, None, s)), s)
+    byts = n * 8 * (3 + 1 + 4 + 16 + 9 + 16 + 4 + 16 + 16)
+    res["predict_dev"] = {"n": n, "kernel_ms": ms, "items_per_s": n / (ms * 1e-3), "gbs": byts / (ms * 1e-3) / 1e9,
+                          "hbm_frac": byts / (ms * 1e-3) / 1e9 / HBM}
+    ms = timed(lambda: check(lib.pekf_correct_dev(n, b["mag"].ptr, b["acc"].ptr, z.ptr, Pm.ptr, Kk.ptr, b["a0"].ptr,
+                                                  b["m0"].ptr, Xo.ptr, Po.ptr, s)), s)
+    byts = n * 8 * (3 + 3 + 4 + 16 + 16 + 3 + 3 + 4 + 16)
+    res["correct_dev"] = {"n": n, "kernel_ms": ms, "items_per_s": n / (ms * 1e-3), "gbs": byts / (ms * 1e-3) / 1e9,
+                          "hbm_frac": byts / (ms * 1e-3) / 1e9 / HBM}
+    log("per-call predict %.2f ms, correct %.2f ms at n=1M" % (res["predict_dev"]["kernel_ms"], ms))
+    return res
+
+
 def main():
     st = engine.Stream()
     s = st.handle
@@ -284,27 +312,7 @@ def main():
     del h
 
     # ---- per-call operators at n = 1M (device pointers)
-    n = 1 << 20
-    rng = np.random.default_rng(0)
-    X = rng.normal(size=(n, 4))
-    X /= np.linalg.norm(X, axis=1, keepdims=True)
-    bufs = {k: engine.DeviceBuffer(a.nbytes).upload(np.ascontiguousarray(a)) for k, a in dict(
-        g=rng.normal(size=(n, 3)), dt=np.full(n, 1e7), X=X, P=np.tile(np.eye(4), (n, 1, 1)),
-        Q=np.tile(np.eye(3), (n, 1, 1)), R=np.tile(np.eye(4) * 0.1, (n, 1, 1)), acc=X[:, :3].copy(),
-        mag=X[:, 1:].copy(), a0=np.tile([0, 0, 1.0], (n, 1)), m0=np.tile([0.5, 0, -0.86], (n, 1))).items()}
-    z, Pm, Kk, Xo, Po = (engine.DeviceBuffer(8 * n * k) for k in (4, 16, 16, 4, 16))
-    b = bufs
-    ms = timed(lambda: check(lib.pekf_predict_dev(n, b["g"].ptr, b["dt"].ptr, b["X"].ptr, b["P"].ptr, b["Q"].ptr,
-                                                  b["R"].ptr, z.ptr, Pm.ptr, Kk.ptr, None, s)), s)
-    byts = n * 8 * (3 + 1 + 4 + 16 + 9 + 16 + 4 + 16 + 16)
-    res["predict_dev"] = {"n": n, "kernel_ms": ms, "items_per_s": n / (ms * 1e-3), "gbs": byts / (ms * 1e-3) / 1e9,
-                          "hbm_frac": byts / (ms * 1e-3) / 1e9 / HBM}
-    ms = timed(lambda: check(lib.pekf_correct_dev(n, b["mag"].ptr, b["acc"].ptr, z.ptr, Pm.ptr, Kk.ptr, b["a0"].ptr,
-                                                  b["m0"].ptr, Xo.ptr, Po.ptr, s)), s)
-    byts = n * 8 * (3 + 3 + 4 + 16 + 16 + 3 + 3 + 4 + 16)
-    res["correct_dev"] = {"n": n, "kernel_ms": ms, "items_per_s": n / (ms * 1e-3), "gbs": byts / (ms * 1e-3) / 1e9,
-                          "hbm_frac": byts / (ms * 1e-3) / 1e9 / HBM}
-    log("per-call predict %.2f ms, correct %.2f ms at n=1M" % (res["predict_dev"]["kernel_ms"], ms))
+    res.update(percall_dev(s))
 
     # ---- per-call latency at n = 1 (host pointers): the ctypes engine wrappers, and the CPython
     # binding the drop-in KalmanFilter.Prediction / Correction use (what main_file.py pays per call)
