@@ -254,6 +254,24 @@ PEKF_DEV double rsqrt(double x) {
     return y;
 }
 
+// sqrt(x) where no reciprocal of it is wanted (same FAST as rsqrt): the seed y, g = x y, then ONE
+// step s = g + y (x - g^2) / 2.  3 operations after the seed where x * rsqrt(x) takes 4, and the same
+// error class: a seed error d <= 5.6e-8 leaves 1.5 d^2 ~ 5e-15 relative; measured <= 36 ulp over
+// 1e-6..1e6, as x * rsqrt(x) (scripts/probe_fp64.hip).  x = 0 gives NaN (0 * inf), as x * rsqrt(x) does.
+PEKF_DEV double fma_half_rn(double a, double b, double c) {  // (c - a b) / 2, omod (see fma_half)
+    double d;
+    asm("v_fma_f64 %0, -%1, %2, %3 div:2" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+template <int FAST>
+PEKF_DEV double sqrt_fast(double x) {
+    if (!FAST) return sqrt(x);
+    const double y = __builtin_amdgcn_rsq(x);
+    const double g = x * y;
+    const double eh = FAST == 2 ? fma_half_rn(g, g, x) : 0.5 * fma(-g, g, x);
+    return fma(eh, y, g);
+}
+
 // ------------------------------- Wahba closed form -------------------------------------------
 
 // Orthonormal frame of a vector pair (a, m): e1 = a/|a|, e2 = GramSchmidt(m), u3 = e1 x e2,
@@ -683,59 +701,54 @@ PEKF_DEV void wahba_matrix_toward(const RW &W, const Reload &reload, const doubl
 
 // Y' = q_W^* (x) Y for the flipped Wahba quaternion Y of the weights (ka, km), in the reference frame's
 // basis (z' the prediction in that basis): Y' = v * sc.  Only the quaternion of R' = Rz(theta) Fv^T is
-// wanted, up to a scale and with the sign of q.z, and R' is a product of three plane rotations whose
-// unnormalised half-angle quaternions come from numbers the frame's Gram-Schmidt forms anyway, so no
-// frame, matrix or Q4 is built:
-//   q_A  the shortest arc taking acc to the x axis:        (|a| + a_x, 0, a_z, -a_y)
-//   q_B  about x, taking t' = A (mag - beta1 e1) to y:     (|t'| + t'_y, -t'_z, 0, 0)
-//   q_th about z by theta, (cos, sin) ~ (p, s):            (h + p, 0, 0, s), h = |(p, s)|
-// and q' ~ q_th (x) q_B (x) q_A.  t' needs no t: A m = m - (e1 + x) (beta1 + m_x) / (1 + e1_x) + 2 beta1 x,
-// whose y and z components, scaled by w = |a| + a_x, are w m_y - a_y u and w m_z - a_z u, u = beta1 + m_x;
-// |t'| w = beta2 w, and (p, s) is taken at the same scale w (alpha w, beta1 w, beta2 w).
+// wanted, up to a scale and with the sign of q.z.  In this basis the reference pair spans the xy plane
+// (acc0 = (aW, 0, 0), mag0 = (b1W, b2W, 0)), so R' is the rotation that takes the measured plane's
+// normal n = a x m to z, followed by the best rotation about z: two plane rotations, whose unnormalised
+// half-angle quaternions need no frame, no Gram-Schmidt, no 1 / |a| and no matrix or Q4:
+//   q_1  the shortest arc taking n to z:                   (N + n_z, n_y, -n_x, 0), N = |n|
+//   q_th about z by theta, (cos, sin) ~ (C, S):            (H + C, 0, 0, S), H = |(C, S)|
+// and q' ~ q_th (x) q_1.  A vector c of the measured plane (c . n = 0) is taken by q_1 = (A0, A1, A2, 0)
+// to A0 (c_x, c_y) + c_z (A2, -A1) times one positive factor, the same for a and m, which drops out of
+// the angle; with a', m' these in-plane coordinates, the 2x2 core of wahba_rotation is
+//   C = ka aW a'_x + km (b1W m'_x + b2W m'_y),   S = km (b2W m'_x - b1W m'_y) - ka aW a'_y.
 // Conditioning.  A half-angle form (1 + cos, sin) cancels near a half turn: its angle error is
 // (eps / 2) tan(phi / 2).  The attitude of a moving body takes every value, so on a real stream some
-// lane of a wave is always near a half turn of q_A or q_B (1 + cos < 1/8 on 6 % and 16 % of the
-// records of the synthetic stream: a branch to another form there would be taken by every wave at
-// every record).  So each arc is taken in the half where it is well conditioned, by selects:
-//   q_A  sigma = sign(a_x): the pair (sigma a, sigma m) has the frame Fv diag(sigma, sigma, 1), i.e.
-//        Fv^T = Rz(pi)^[sigma < 0] Fv_sigma^T, and the half turn about z adds to theta: (p, s) ->
-//        sigma (p, s).  Every sigma below is the sign bit of a_x copied onto a factor that is formed
-//        anyway (1/|a|, 1/|t'|), and q_A is used times sigma: (sigma w, 0, a_z, -a_y), w = |a| + |a_x|.
-//   q_B, q_th  a plane rotation (C, S) of length H has the half-angle quaternion (H + C, S) and, up to a
+// lane of a wave is always near a half turn of one of the arcs (a branch to another form there would be
+// taken by every wave at every record).  So each arc is taken in the half where it is well
+// conditioned, by selects:
+//   q_1  w = N + |n_z|.  n_z >= 0: (w, n_y, -n_x).  n_z < 0: the same quaternion times N - n_z = w,
+//        (rho2, w n_y, -w n_x), where rho2 = (N - n_z)(N + n_z) is formed without cancellation as
+//        n_x^2 + n_y^2: no second square root.  Either form is valid on both sides of n_z = 0 (+-0 too).
+//   q_th a plane rotation (C, S) of length H has the half-angle quaternion (H + C, S) and, up to a
 //        factor S / (H + C), (S, H - C): the first for C >= 0, the second for C < 0, so that the sum is
 //        H + |C| >= H in both (arcs of at most a quarter turn: angle error <= eps / 2).
-// The factor's sign is free: the result takes the sign of q'.z at the end.
+// The factor's sign is free: the result takes the sign of q'.z at the end.  N and H are square roots of
+// which no reciprocal is used (sqrt_fast).
 // The state-independent half (it depends on the record's samples only, not on the prediction z), for
-// ekf_record_step's HOIST schedule: q' unnormalised.  km < 0 (|acc_z| > 1, the reflection case of
-// wahba_sign) is not handled here: wahba_toward_from_product sends it to the matrix chain.
+// ekf_record_step's HOIST schedule: q' unnormalised.  Inputs it does not serve, all sent to the matrix
+// chain by wahba_toward_from_product: km < 0 (|acc_z| > 1, the reflection case of wahba_sign); a zero
+// sample or acc parallel to mag (n = 0, N = 0 * inf = NaN, so q' NaN); and rho2 = 0 with n_z < 0 (q' = 0,
+// so its scale is NaN), which needs a_z = m_z = 0, hence ka = 0: a rank-1 B exactly in the xy plane.
 template <int F = 1, class RW, std::enable_if_t<RW::kRefBasis, int> = 0>
 PEKF_DEV void wahba_product_ref(const RW &W, const double *a, const double *m, double ka, double km, double *q) {
-    const double sa = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
-    const double ias = copysign(rsqrt<F>(sa), a[0]);
-    const double nas = sa * ias;                                            // sigma |a|
-    const double ws = nas + a[0];                                           // sigma w
-    const double b1s = (a[0] * m[0] + a[1] * m[1] + a[2] * m[2]) * ias;     // sigma beta1
-    const double us = b1s + m[0];                                           // sigma u
-    const double tys = ws * m[1] - a[1] * us;                               // w t'_y of (sigma a, sigma m)
-    const double ntz = a[2] * us - ws * m[2];                               // -w t'_z
-    const double sb = tys * tys + ntz * ntz;
-    const double hs = sb * copysign(rsqrt<F>(sb), a[0]);                    // sigma beta2 w
-    const double kw = km * W.b2W, kb = km * W.b1W;
-    const double aw = fabs(nas) * ws, b1w = b1s * fabs(ws);                 // sigma alpha w, sigma beta1 w
-    const double p = ka * W.aW * aw + kb * b1w + kw * hs;                   // sigma w (p, s) of wahba_rotation
-    const double s = kw * b1w - kb * hs;
-    const double n = p * p + s * s;
-    const double h = n * rsqrt<F>(n);
-    const double wt = h + fabs(p), wb = fabs(hs) + fabs(tys);
-    const bool ft = p >= 0.0, fb = tys >= 0.0;
-    const double c0 = ft ? wt : s, c3 = ft ? s : wt;                        // q_th = (c0, 0, 0, c3)
-    const double b0 = fb ? wb : ntz, b1 = fb ? ntz : wb;                    // q_B = (b0, b1, 0, 0)
-    // r = q_B (x) sigma q_A, then q' = q_th (x) r
-    const double r0 = b0 * ws, r1 = b1 * ws, r2 = b0 * a[2] + b1 * a[1], r3 = b1 * a[2] - b0 * a[1];
-    q[0] = c0 * r0 - c3 * r3;
-    q[1] = c0 * r1 - c3 * r2;
-    q[2] = c0 * r2 + c3 * r1;
-    q[3] = c0 * r3 + c3 * r0;
+    const double nx = a[1] * m[2] - a[2] * m[1], ny = a[2] * m[0] - a[0] * m[2], nz = a[0] * m[1] - a[1] * m[0];
+    const double rho2 = nx * nx + ny * ny;
+    const double w = sqrt_fast<F>(rho2 + nz * nz) + fabs(nz);
+    const bool f1 = nz >= 0.0;
+    // q_1 = (A0, A1, -B2, 0): the negation rides on the products below
+    const double A0 = f1 ? w : rho2, A1 = f1 ? ny : w * ny, B2 = f1 ? nx : w * nx;
+    const double ax = A0 * a[0] - B2 * a[2], ay = A0 * a[1] - A1 * a[2];                // a', m'
+    const double mx = A0 * m[0] - B2 * m[2], my = A0 * m[1] - A1 * m[2];
+    const double kaw = ka * W.aW, kb = km * W.b1W, kw = km * W.b2W;
+    const double C = kaw * ax + kb * mx + kw * my;
+    const double S = kw * mx - kb * my - kaw * ay;
+    const double wt = sqrt_fast<F>(C * C + S * S) + fabs(C);
+    const bool ft = C >= 0.0;
+    const double c0 = ft ? wt : S, c3 = ft ? S : wt;                                    // q_th = (c0, 0, 0, c3)
+    q[0] = c0 * A0;
+    q[1] = c0 * A1 + c3 * B2;
+    q[2] = c3 * A1 - c0 * B2;
+    q[3] = c3 * A0;
 }
 
 // The z-dependent half: q' scaled to unit length with the sign of q'.z, and the fallback to the matrix

@@ -3,7 +3,7 @@
 // per launch) of 40 B records, and the same loop over FP64 records (pekf_run_rec64_dev: recorded
 // logs).  A file of its own because it is compiled with the max-ILP machine scheduler
 // (Makefile RUNMULTIFLAGS): the time loop's record is ~300 dependent FP64 VALU instructions with
-// seven transcendental seeds, and at its 3-4 waves per SIMD (1 at config 2) the interleaving the
+// six transcendental seeds, and at its 3-4 waves per SIMD (1 at config 2) the interleaving the
 // scheduler finds is worth more than the occupancy-first default (same box: config 3 -0.9 %,
 // config 2 -4.5 %, profiles/r2/ab_sched_maxilp/).  The one-record and per-record kernels, which move
 // state through HBM and want occupancy, stay in pekf_run.hip with the default scheduler.

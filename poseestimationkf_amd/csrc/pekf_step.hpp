@@ -275,6 +275,9 @@ __device__ __forceinline__ void record_correct(double *x, const double *z, Sym4T
 // every record after a launch's first).  gy = the gyro sample, dt_ns = T - previousT, missing: the
 // record has no magnetometer sample (record_skip).  Shared by the fused stream kernels, k_live and
 // the handle's per-record update, so all give bit-identical results for the same inputs.
+// In the reference frame's basis the measurement is Wahba's quaternion as a product of two plane
+// rotations (wahba_product_ref: the measured plane's normal to z, then the best turn about z), scaled
+// and flipped toward z by wahba_toward_from_product; in the world basis it is the matrix chain.
 // reload(acc, mag) re-reads the record's samples for the rare degenerate-Wahba fallback
 // (wahba_toward_from_product); it is not called on the common path.
 // MC (the multi-record loop): the covariance is carried as N (StepK), and X is left unnormalised,
