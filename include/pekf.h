@@ -320,6 +320,24 @@ int pekf_live_dev(int64_t batch, int64_t n_events, const void *ev_planes, const 
 int pekf_live_ext_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
                       const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
                       int32_t *counts, double *refs, uint32_t flags, int *dev_error, void *stream);
+/* pekf_live_ext_dev with a pose per record: what the server does with every phase-3 record --
+ * Parser::ExecuteKalmanFilter (KFS/Parser.cpp:248-267) hands it to the filter and the resulting X_k goes to
+ * the plotter and into the log's "X_k :" line.  Flags and every check as pekf_live_ext_dev; X, P, counts and
+ * refs come out exactly as from it.
+ * traj[traj_rows][batch][4] (device, 16-byte aligned, required when traj_rows > 0): row r of filter b is its X
+ * after the r-th record it applied in this launch -- the unit, world-basis quaternion, formed as pekf_run_dev's
+ * trajectory row and as the launch's final X are, so row counts[b] - 1 equals X[b] bit for bit.  The row index
+ * is the filter's own record index, not a time step shared by the batch: filters complete records at different
+ * events.  traj_dt[traj_rows][batch] (device, may be NULL): the same record's dt in float64 ns as the filter
+ * applied it (the dt word, an escaped record's float64 dt, or an FP64 event's time difference).
+ * Nothing else is written: rows >= counts[b], rows >= traj_rows, every row of a filter that is not ready and of
+ * a stream without records keep what the caller put there (fill with 0xFF bytes to read them as NaN);
+ * counts[b] still reports every record applied, also above traj_rows.  0 <= traj_rows < 2^31;
+ * traj_rows == 0 is pekf_live_ext_dev itself (traj and traj_dt are not looked at). */
+int pekf_live_traj_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                       const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
+                       int32_t *counts, double *refs, uint32_t flags, double *traj, double *traj_dt,
+                       int64_t traj_rows, int *dev_error, void *stream);
 
 /* Phase 2 of the server's Parser (KFS/Parser.cpp:36-58,84-140; KFS/InitialValues.cpp) on the device: per
  * filter, the mean and sample variance of the first n_avg (the server: 100) samples of each sensor type,

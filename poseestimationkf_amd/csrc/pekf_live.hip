@@ -23,344 +23,25 @@
 // when every block drains).  Per lane the records apply in order with the same arithmetic as
 // pekf_run_dev's multi-record kernel (reference basis, N, omod), so the final state equals the split
 // pipeline's bit for bit (with f32 records; with FP64 ones, within FP64 rounding of the unrounded chain).
-#include "pekf_phase3.hpp"
-#include "pekf_step.hpp"
-
-namespace pekf {
-
-// Tuned on the box (scripts/ab_live.sh, profiles/r2/live/): the kernel is register-bound -- front-end
-// state, filter state and a filter step's temporaries -- so the record queue lives in LDS and the
-// launch is held to 2 waves per SIMD (252 registers) with a 3-event ring: 5.5 ms at 1M filters x
-// 1,024 events, against 8.7 ms for 6 events and the queue in registers at 1 wave/SIMD.  Queueing the
-// records' raw inputs instead (emit moved into the filter step, 104 B per slot, 3 deep) was slower:
-// 5.9 ms (profiles/r2/live/variants/raw_queue.log).
-#ifndef PEKF_LIVE_RING
-#define PEKF_LIVE_RING 3  // event rows in flight per lane; a filter step may run after each block of them
-#endif
-#ifndef PEKF_LIVE_RING64
-#define PEKF_LIVE_RING64 3  // the same for FP64 events (32 B each)
-#endif
-#ifndef PEKF_LIVE_NTL
-#define PEKF_LIVE_NTL 1  // non-temporal event loads: each event is read once (-1.4 %, profiles/r4/ntload/)
-#endif
-#ifndef PEKF_LIVE_QUEUE
-#define PEKF_LIVE_QUEUE 6  // records a lane can hold (48 B of LDS each: the 40 B record + its escaped dt)
-#endif
-#ifndef PEKF_LIVE_QUEUE64
-#define PEKF_LIVE_QUEUE64 5  // the same with FP64 acc / mag (64 B each): 20 KB of LDS per wave, all of it
-#endif
-#ifndef PEKF_LIVE_QUEUE_EV64
-#define PEKF_LIVE_QUEUE_EV64 4  // FP64 events: all-FP64 records (80 B each), 20 KB of LDS per wave
-#endif
-#ifndef PEKF_LIVE_QUORUM
-#define PEKF_LIVE_QUORUM 56  // lanes of 64 with a queued record that trigger a filter step
-#endif
-#ifndef PEKF_LIVE_EV64_WAVES
-#define PEKF_LIVE_EV64_WAVES 2
-#endif
-
-// A lane's records waiting for the wave's next filter step, oldest first: a ring of Q slots per lane in
-// LDS, [slot][lane] so that a wave's accesses fall in distinct banks whatever slot each lane is at.  A
-// push or pop is a few address operations and three LDS accesses.  (Held in registers -- slots as
-// separate variables, a push selecting its slot -- the queue cost 40 selects per push and registers
-// the kernel does not have: profiles/r2/live/variants/live_ab*.log.)
-// A record whose dt does not fit its dt word (PEKF_DT_ESCAPE, a pause of 2^31 ns or more) keeps its
-// float64 dt in the slot's side entry dt[slot][lane], written and read only for such a record.
-template <int Q>
-struct LdsQueue {
-    static constexpr size_t kBytes = (sizeof(float4) * 2 + sizeof(float2) + sizeof(double)) * Q * kRunBlock;
-    float4 (*gd)[kRunBlock];
-    float4 (*am)[kRunBlock];
-    float2 (*my)[kRunBlock];
-    double (*dt)[kRunBlock];
-    int head = 0, n = 0;
-    __device__ __forceinline__ void bind(unsigned char *lds) {
-        gd = reinterpret_cast<float4(*)[kRunBlock]>(lds);
-        am = reinterpret_cast<float4(*)[kRunBlock]>(lds + sizeof(float4) * Q * kRunBlock);
-        dt = reinterpret_cast<double(*)[kRunBlock]>(lds + 2 * sizeof(float4) * Q * kRunBlock);
-        my = reinterpret_cast<float2(*)[kRunBlock]>(lds + (2 * sizeof(float4) + sizeof(double)) * Q * kRunBlock);
-    }
-    __device__ __forceinline__ int tail() const { return head + n < Q ? head + n : head + n - Q; }
-    __device__ __forceinline__ bool esc_queued() const { return false; }  // escaped dts live in the dt plane
-    __device__ __forceinline__ void push(const Rec &r, bool esc, double dtv) {
-        const int slot = tail();
-        gd[slot][threadIdx.x] = r.gd;
-        am[slot][threadIdx.x] = r.am;
-        my[slot][threadIdx.x] = r.my;
-        if (esc) dt[slot][threadIdx.x] = dtv;
-        ++n;
-    }
-    using Slot = Rec;
-    // the oldest record and its dt in ns
-    __device__ __forceinline__ Slot pop(double &dtv) {
-        const Rec r = {gd[head][threadIdx.x], am[head][threadIdx.x], my[head][threadIdx.x]};
-        const uint32_t word = __float_as_uint(r.gd.w) & PEKF_DT_MASK;
-        dtv = (double)word;
-        if (word == PEKF_DT_ESCAPE) dtv = dt[head][threadIdx.x];
-        if (n > 0) {
-            head = head + 1 < Q ? head + 1 : 0;
-            --n;
-        }
-        return r;
-    }
-    static __device__ __forceinline__ void unpack(const Slot &r, double (&gy)[3], double (&acc)[3], double (&mag)[3]) {
-        gy[0] = r.gd.x; gy[1] = r.gd.y; gy[2] = r.gd.z;
-        acc[0] = r.am.x; acc[1] = r.am.y; acc[2] = r.am.z;
-        mag[0] = r.am.w; mag[1] = r.my.x; mag[2] = r.my.y;
-    }
-    // the popped record's acc / mag again (it stays in its slot, the one before head, until a later push)
-    __device__ __forceinline__ void reload(double *a, double *m) const {
-        const int slot = head == 0 ? Q - 1 : head - 1;
-        const float4 va = am[slot][threadIdx.x];
-        const float2 vm = my[slot][threadIdx.x];
-        a[0] = va.x; a[1] = va.y; a[2] = va.z;
-        m[0] = va.w; m[1] = vm.x; m[2] = vm.y;
-    }
-};
-
-// The queue with FP64 acc / mag: what the server's filter receives (KFS/KalmanFilter.cpp:279-303 hands
-// the double low-pass outputs to Prediction / Correction), not the f32 stream record.  Per slot the
-// gyro / dt word (16 B) and acc and mag as three double2 planes (48 B): 5 slots x 64 B x 64 lanes is
-// 20 KB per wave, exactly the CU's 160 KB at 2 waves per SIMD, so there is no room for an escaped-dt
-// plane.  A record whose dt does not fit the dt word keeps its float64 dt in a register instead
-// (esc_dt), one per lane: k_live steps a wave while any lane still has such a record queued, so a lane
-// never holds two (escapes are pauses of 2.1 s or more: rare, and cheap to drain for).
-template <int Q>
-struct LdsQueue64 {
-    static constexpr size_t kBytes = (sizeof(float4) + 3 * sizeof(double2)) * Q * kRunBlock;
-    float4 (*gd)[kRunBlock];
-    double2 (*am)[3][kRunBlock];  // {acc.x, acc.y}, {acc.z, mag.x}, {mag.y, mag.z}
-    double esc_dt = __builtin_nan("");  // the queued escaped record's dt (NaN: none queued)
-    int head = 0, n = 0;
-    __device__ __forceinline__ void bind(unsigned char *lds) {
-        am = reinterpret_cast<double2(*)[3][kRunBlock]>(lds);
-        gd = reinterpret_cast<float4(*)[kRunBlock]>(lds + 3 * sizeof(double2) * Q * kRunBlock);
-    }
-    // a lane has an escaped record queued (k_live then steps until it is applied)
-    __device__ __forceinline__ bool esc_queued() const { return esc_dt == esc_dt; }
-    __device__ __forceinline__ void push(const float4 &g, const V3 &a, const V3 &m, bool esc, double dtv) {
-        const int slot = head + n < Q ? head + n : head + n - Q;
-        gd[slot][threadIdx.x] = g;
-        am[slot][0][threadIdx.x] = make_double2(a.x, a.y);
-        am[slot][1][threadIdx.x] = make_double2(a.z, m.x);
-        am[slot][2][threadIdx.x] = make_double2(m.y, m.z);
-        if (esc) esc_dt = dtv;
-        ++n;
-    }
-    struct Slot {
-        float4 gd;
-        double2 v[3];
-    };
-    __device__ __forceinline__ Slot pop(double &dtv) {
-        const Slot r = {gd[head][threadIdx.x], {am[head][0][threadIdx.x], am[head][1][threadIdx.x], am[head][2][threadIdx.x]}};
-        const uint32_t word = __float_as_uint(r.gd.w) & PEKF_DT_MASK;
-        dtv = (double)word;
-        if (n > 0 && word == PEKF_DT_ESCAPE) {
-            dtv = esc_dt;
-            esc_dt = __builtin_nan("");
-        }
-        if (n > 0) {
-            head = head + 1 < Q ? head + 1 : 0;
-            --n;
-        }
-        return r;
-    }
-    static __device__ __forceinline__ void unpack(const Slot &r, double (&gy)[3], double (&acc)[3], double (&mag)[3]) {
-        gy[0] = r.gd.x; gy[1] = r.gd.y; gy[2] = r.gd.z;
-        acc[0] = r.v[0].x; acc[1] = r.v[0].y; acc[2] = r.v[1].x;
-        mag[0] = r.v[1].y; mag[1] = r.v[2].x; mag[2] = r.v[2].y;
-    }
-    __device__ __forceinline__ void reload(double *a, double *m) const {
-        const int slot = head == 0 ? Q - 1 : head - 1;
-        const double2 v0 = am[slot][0][threadIdx.x], v1 = am[slot][1][threadIdx.x], v2 = am[slot][2][threadIdx.x];
-        a[0] = v0.x; a[1] = v0.y; a[2] = v1.x;
-        m[0] = v1.y; m[1] = v2.x; m[2] = v2.y;
-    }
-};
-
-// The queue of FP64-event launches: every field of the record in FP64 -- gyro and dt too, as the server's
-// filter gets them (dt any float64, so no escape) -- 80 B per slot as five double2 planes [slot][lane]
-// (16 B per lane and plane: conflict-free ds_*_b128), 4 deep = 20 KB per wave, the CU's 160 KB at 2
-// waves per SIMD.
-template <int Q>
-struct LdsQueueF64 {
-    static constexpr size_t kBytes = 5 * sizeof(double2) * Q * kRunBlock;
-    double2 (*v)[5][kRunBlock];  // {gx, gy}, {gz, dt}, {ax, ay}, {az, mx}, {my, mz}
-    int head = 0, n = 0;
-    __device__ __forceinline__ void bind(unsigned char *lds) { v = reinterpret_cast<double2(*)[5][kRunBlock]>(lds); }
-    __device__ __forceinline__ bool esc_queued() const { return false; }
-    __device__ __forceinline__ void push(const double4 &g, const V3 &a, const V3 &m) {
-        const int slot = head + n < Q ? head + n : head + n - Q;
-        v[slot][0][threadIdx.x] = make_double2(g.x, g.y);
-        v[slot][1][threadIdx.x] = make_double2(g.z, g.w);
-        v[slot][2][threadIdx.x] = make_double2(a.x, a.y);
-        v[slot][3][threadIdx.x] = make_double2(a.z, m.x);
-        v[slot][4][threadIdx.x] = make_double2(m.y, m.z);
-        ++n;
-    }
-    struct Slot {
-        double2 v[5];
-    };
-    __device__ __forceinline__ Slot pop(double &dtv) {
-        Slot r;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) r.v[k] = v[head][k][threadIdx.x];
-        dtv = r.v[1].y;
-        if (n > 0) {
-            head = head + 1 < Q ? head + 1 : 0;
-            --n;
-        }
-        return r;
-    }
-    static __device__ __forceinline__ void unpack(const Slot &r, double (&gy)[3], double (&acc)[3], double (&mag)[3]) {
-        gy[0] = r.v[0].x; gy[1] = r.v[0].y; gy[2] = r.v[1].x;
-        acc[0] = r.v[2].x; acc[1] = r.v[2].y; acc[2] = r.v[3].x;
-        mag[0] = r.v[3].y; mag[1] = r.v[4].x; mag[2] = r.v[4].y;
-    }
-    __device__ __forceinline__ void reload(double *a, double *m) const {
-        const int slot = head == 0 ? Q - 1 : head - 1;
-        const double2 v2 = v[slot][2][threadIdx.x], v3 = v[slot][3][threadIdx.x], v4 = v[slot][4][threadIdx.x];
-        a[0] = v2.x; a[1] = v2.y; a[2] = v3.x;
-        m[0] = v3.y; m[1] = v4.x; m[2] = v4.y;
-    }
-};
-
-// TE: the event planes may hold time events (Phase3::event).  R64: records keep their FP64 acc / mag
-// (LdsQueue64); otherwise they are the f32 stream records pekf_frontend_dev writes (LdsQueue).
-// EV64: FP64 events (PEKF_EV_F64_EVENTS, double4 planes: the server's own sample values), records all
-// FP64 (LdsQueueF64); TE and R64 do not apply.
-template <bool TE, bool R64, bool EV64 = false>
-__global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 ? PEKF_LIVE_EV64_WAVES : 2))) void k_live(
-    int64_t batch, int64_t n_events, const std::conditional_t<EV64, double4, float4> *__restrict__ ev,
-    const double *__restrict__ init, const int64_t *__restrict__ t_init, double alpha, double qs, double rs,
-    double *__restrict__ Xio, double *__restrict__ Pio, int32_t *__restrict__ counts, double *__restrict__ refs) {
-    using EvT = std::conditional_t<EV64, double4, float4>;
-    constexpr int kRing = EV64 ? PEKF_LIVE_RING64 : PEKF_LIVE_RING, kFlush = 3, kQuorum = PEKF_LIVE_QUORUM;
-    constexpr int kQueue = EV64 ? PEKF_LIVE_QUEUE_EV64 : R64 ? PEKF_LIVE_QUEUE64 : PEKF_LIVE_QUEUE;
-    constexpr int kPush = kRing / kFlush;  // records a lane can complete within one block
-    static_assert(kRing % kFlush == 0, "the ring depth must be a multiple of the emit period");
-    static_assert(kQueue >= kPush, "the queue must hold a block's records");
-    static_assert(!(EV64 && (TE || R64)), "FP64 events take their own record queue and carry their times");
-    // LdsQueue64 keeps ONE escaped dt per lane (esc_dt) and want_step drains it before the next block,
-    // which is safe only while a block completes at most one record per lane
-    static_assert(!R64 || kPush == 1, "LdsQueue64's single escaped-dt register needs one record per lane per block");
-    const int64_t b = (int64_t)blockIdx.x * kRunBlock + threadIdx.x;
-    if (b >= batch) return;
-
-    Phase3T<std::conditional_t<EV64, V3, F3>> fe;
-    fe.start(init + 6 * b, t_init[b], alpha);
-    // a filter that never finished phase 2 (non-finite init: pekf_frontend_init_dev's "not ready")
-    // applies no record: its state is left as it was and counts[b] = 0
-    const bool ready = init_is_finite(init + 6 * b);
-    double rf[6];
-    fe.refs(rf);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) refs[6 * b + k] = rf[k];
-
-    // the filter in its reference frame's basis, covariance as N (pekf_step.hpp), as k_run does it
-    Frame Wf;
-    make_frame<true>(rf, rf + 3, Wf);
-    double x[4];
-    Sym4T<double> P;
-    load_state<false>(Xio, Pio, b, batch, x, P);
-    const RefWLazy Wr = enter_ref_basis<false>(Wf, refs + 6 * b, false, x, P, rs);
-    const StepK<double> kc = step_consts<double, true>(qs, rs);
-
-    using Queue = std::conditional_t<EV64, LdsQueueF64<kQueue>,
-                                     std::conditional_t<R64, LdsQueue64<kQueue>, LdsQueue<kQueue>>>;
-    __shared__ __attribute__((aligned(16))) unsigned char q_lds[Queue::kBytes];
-    Queue queue;
-    queue.bind(q_lds);
-    int32_t applied = 0;
-    // One filter step for every lane with a queued record: its oldest, Prediction + Correction with
-    // the multi-record kernel's arithmetic (the first record of the launch from the loaded |X|^2,
-    // every later one lazy; front-end records always carry a magnetometer sample).
-    auto filter_step = [&]() {
-        const bool has = queue.n > 0;
-        double dt;
-        const typename Queue::Slot cur = queue.pop(dt);
-        auto reload = [&](double *a, double *m) { queue.reload(a, m); };  // rare: the degenerate-Wahba fallback
-        OmodMode mode;
-        mode.enter();
-        if (has) {
-            double gy[3], acc[3], mag[3];
-            Queue::unpack(cur, gy, acc, mag);
-            if (applied == 0)
-                ekf_record_step<double, true, false, true>(x, state_norm2(x), P, Wr, kc, gy, dt, false, acc, mag,
-                                                           reload);
-            else
-                ekf_record_step<double, true, true, true>(x, 1.0, P, Wr, kc, gy, dt, false, acc, mag, reload);
-            ++applied;
-        }
-        mode.leave();
-    };
-    // the pending record (captured by Phase3::event) into the queue
-    auto push_pending = [&](const auto &q) {
-        bool esc;
-        if constexpr (EV64) {
-            const double4 g = fe.emit64(q);
-            if (ready) queue.push(g, fe.lpf_acc, fe.lpf_mag);
-        } else if constexpr (R64) {
-            const float4 g = fe.emit_lpf(q, esc);
-            if (ready) queue.push(g, fe.lpf_acc, fe.lpf_mag, esc, q.dt);
-        } else {
-            const Rec rc = fe.emit(q, esc);
-            if (ready) queue.push(rc, esc, q.dt);
-        }
-    };
-    auto flush = [&]() {
-        if (fe.pend) {
-            fe.pend = false;
-            push_pending(fe.p);
-        }
-    };
-
-    // wave-uniform: a step while some lane could overflow in the next block, then one more if a quorum
-    // of lanes has a record; after the last event until every queue is empty; (R64) while some lane
-    // still has an escaped record queued, so the next block cannot queue a second one on that lane
-    auto want_step = [&](bool last) {
-        const uint64_t queued = __ballot(queue.n > 0);
-        return queued != 0 && (last || __any(queue.n > kQueue - kPush) || __popcll(queued) >= kQuorum ||
-                               (R64 && !EV64 && __any(queue.esc_queued())));
-    };
-    auto steps = [&](bool last) {
-        // tested before the loop, so a block that runs no step does not pass the loop's header
-        if (want_step(last)) {
-            do {
-                filter_step();
-            } while (want_step(last));
-        }
-    };
-    // The events come through the load-ahead ring (pekf_phase3.hpp: event_ring; its null events move no
-    // state, with or without TE); nothing is pending after a whole block, and a filter step may follow it.
-    event_ring<kRing, PEKF_LIVE_NTL>(
-        ev, batch, (uint32_t)b, (int32_t)n_events,
-        [&](int k, const EvT &v4) {
-            if constexpr (EV64)
-                fe.event64(v4);
-            else
-                fe.template event<TE>(v4);
-            if ((k + 1) % kFlush == 0) flush();
-        },
-        steps);
-    counts[b] = applied;
-    if (applied == 0) return;  // no record: the state is left as it was (as pekf_run_dev with counts)
-    from_ref_basis(Wr, x, P, rs);
-    store_state<false>(Xio, Pio, b, batch, x, P);
-}
-
-}  // namespace pekf
+#include "pekf_live.hpp"
 
 using namespace pekf;
 
-extern "C" int pekf_live_ext_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
-                                 const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
-                                 int32_t *counts, double *refs, uint32_t flags, int *dev_error, void *stream) {
+// the checks behind every pekf_live_* entry; traj_rows == 0: the kernels without trajectory output, which
+// this file instantiates (and no others: tests/test_omod_listing.py counts them)
+static int launch_live(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                       const int64_t *t_init, double alpha, double *X, double *P, double q, double r, int32_t *counts,
+                       double *refs, uint32_t flags, double *traj, double *traj_dt, int64_t traj_rows, int *dev_error,
+                       void *stream) {
     PEKF_CHECK_ARG(batch >= 0 && n_events >= 0, "negative size");
     PEKF_CHECK_ARG((flags & ~(PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS | PEKF_EV_F64_EVENTS)) == 0, "unknown flags");
     const bool ev64 = (flags & PEKF_EV_F64_EVENTS) != 0;
     PEKF_CHECK_ARG(!ev64 || (flags & (PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS)) == 0,
                    "PEKF_EV_F64_EVENTS takes no other flag (FP64 events carry their times; their records are FP64)");
+    PEKF_CHECK_ARG(traj_rows >= 0 && traj_rows < ((int64_t)1 << 31), "traj_rows must be >= 0 and < 2^31");
+    PEKF_CHECK_ARG(traj_rows == 0 || (traj && (uintptr_t)traj % 16 == 0),
+                   "traj must be a 16-byte aligned pointer when traj_rows > 0");
+    PEKF_CHECK_ARG(traj_rows == 0 || (uintptr_t)traj_dt % 8 == 0, "misaligned traj_dt");
     if (batch == 0) return PEKF_OK;
     PEKF_CHECK_ARG(batch < ((int64_t)1 << 28), "batch must be < 2^28 filters per launch");
     PEKF_CHECK_ARG(n_events < ((int64_t)1 << 30), "n_events must be < 2^30 per launch");
@@ -368,18 +49,26 @@ extern "C" int pekf_live_ext_dev(int64_t batch, int64_t n_events, const void *ev
     PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
     PEKF_CHECK_ARG(r > 0.0, "r must be > 0 (S = P- + rI must be SPD)");
     (void)dev_error;  // every record's dt is applied (escaped ones from the queue's side entries)
-    const dim3 grid(grid_for(batch, kRunBlock)), block(kRunBlock);
-    auto launch = [&](auto kernel, const auto *ev) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, as_stream(stream), batch, n_events, ev, init, t_init, alpha, q, r, X,
-                           P, counts, refs);
-    };
-    if (ev64)  // the one FP64-event variant
-        launch(k_live<false, false, true>, static_cast<const double4 *>(ev_planes));
-    else
-        dispatch_bools(
-            [&](auto te, auto r64) { launch(k_live<te.value, r64.value>, static_cast<const float4 *>(ev_planes)); },
-            (flags & PEKF_EV_TIME_EVENTS) != 0, (flags & PEKF_EV_F32_RECORDS) == 0);
-    return launched("k_live");
+    if (traj_rows > 0)  // the TRAJ twins: pekf_live_traj.hip
+        return launch_live_traj(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, traj,
+                                traj_dt, (int32_t)traj_rows, as_stream(stream));
+    return launch_k_live<false>(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, nullptr,
+                                nullptr, 0, as_stream(stream));
+}
+
+extern "C" int pekf_live_traj_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                                  const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
+                                  int32_t *counts, double *refs, uint32_t flags, double *traj, double *traj_dt,
+                                  int64_t traj_rows, int *dev_error, void *stream) {
+    return launch_live(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, traj, traj_dt,
+                       traj_rows, dev_error, stream);
+}
+
+extern "C" int pekf_live_ext_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                                 const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
+                                 int32_t *counts, double *refs, uint32_t flags, int *dev_error, void *stream) {
+    return launch_live(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, nullptr,
+                       nullptr, 0, dev_error, stream);
 }
 
 extern "C" int pekf_live_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,

@@ -524,7 +524,52 @@ def _record_flags(records, events="f32"):
     return EV_F32_RECORDS if records == "f32" else 0
 
 
-def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", events="f32", calibration=None):
+def trajectory_rows(trajectory, n_events):
+    """The sessions' trajectory argument as a row count: False / None 0 (no trajectory), True n_events // 3
+    (a record needs a gyro, an acc and a mag event after the previous one, so no filter has more), an int that
+    many rows (records past them are applied and counted, not stored)."""
+    if trajectory is None or trajectory is False:
+        return 0
+    if trajectory is True:
+        return int(n_events) // 3
+    rows = int(trajectory)
+    if rows < 0 or rows >= 1 << 31:
+        raise ValueError("trajectory must be True, False or a row count in [0, 2^31)")
+    return rows
+
+
+def record_times_ns(t_init, record_dt_ns):
+    """The records' times: t_init (K,) plus the running sum of record_dt_ns (R, K) down each column, in
+    float64 on the host (the server's T of each record, ExtendedKalmanFilter.py:62,67); the rows a filter
+    did not write (NaN dt) and every row after them are NaN."""
+    dt = np.asarray(record_dt_ns, np.float64)
+    return np.asarray(t_init, np.float64)[None, :] + np.cumsum(dt, axis=0)
+
+
+class _Trajectory:
+    """The device buffers of a session's per-record output (pekf_live_traj_dev's traj / traj_dt), every byte
+    0xFF so that what the kernel does not write reads as NaN; rows == 0: nothing is allocated."""
+
+    def __init__(self, trajectory, n_events, batch, stream=None):
+        self.rows, self.batch = trajectory_rows(trajectory, n_events), batch
+        self.traj = self.dt = None
+        if self.rows:
+            self.traj, self.dt = DeviceBuffer(32 * self.rows * batch), DeviceBuffer(8 * self.rows * batch)
+            check(lib.pekf_memset(self.traj.ptr, 0xFF, self.traj.nbytes, stream))
+            check(lib.pekf_memset(self.dt.ptr, 0xFF, self.dt.nbytes, stream))
+
+    def result(self, t_init):
+        """dict(trajectory (R, K, 4), record_dt_ns (R, K), record_times_ns (R, K)), after the launch's sync"""
+        R, K = self.rows, self.batch
+        if R:
+            tr, dt = self.traj.download((R, K, 4), np.float64), self.dt.download((R, K), np.float64)
+        else:
+            tr, dt = np.empty((0, K, 4)), np.empty((0, K))
+        return dict(trajectory=tr, record_dt_ns=dt, record_times_ns=record_times_ns(t_init, dt))
+
+
+def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", events="f32", calibration=None,
+                trajectory=False):
     """A whole client session of the server on the device (KFS/Parser.cpp:28-72): phase-2 events ->
     initial means and start time (pekf_frontend_init_dev) -> phase-3 events -> records -> the filters'
     state (pekf_live_dev), the phase-2 results handed over in device memory.  phase3's times continue
@@ -536,7 +581,11 @@ def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", ev
     KFS/Parser.cpp:107,239), and the returned dict has calibrated (K,) bool.  None: no correction, no launch.
     Returns dict(ready (K,) bool -- a filter
     that never finished phase 2 has NaN references, applies no record and keeps its state --, counts
-    (K,) records applied, refs (K, 6))."""
+    (K,) records applied, refs (K, 6)).
+    trajectory: True or a row cap R (True: phase 3's events // 3, which no filter exceeds) adds a pose per
+    record, from the same launch (pekf_live_traj_dev): trajectory (R, K, 4) -- row r of filter k is its X
+    after its own r-th record, the server's X_k --, record_dt_ns (R, K) the dt it was applied with and
+    record_times_ns (R, K) its time (record_times_ns()); NaN from row counts[k] on."""
     K = filters.batch
     assert np.asarray(phase2["types"]).shape[1] == K and np.asarray(phase2["types"]).shape[0] > 0
     assert np.asarray(phase3["types"]).shape[1] == K
@@ -551,10 +600,14 @@ def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", ev
     check(lib.pekf_frontend_init_ext_dev(K, E2, ev2.ptr, tsb.ptr, int(n_avg), ib.ptr, tib.ptr, None, rb.ptr,
                                          flags2 & EV_F64_EVENTS, None))
     cnt, refs = DeviceBuffer(4 * K), DeviceBuffer(48 * K)
-    filters.run_events_async(ev3, E3, ib, tib, cnt, refs, alpha, flags=flags3 | _record_flags(records, events))
+    tj = _Trajectory(trajectory, E3, K)
+    filters.run_events_async(ev3, E3, ib, tib, cnt, refs, alpha, flags=flags3 | _record_flags(records, events),
+                             traj=tj.traj, traj_dt=tj.dt, traj_rows=tj.rows)
     check(lib.pekf_device_sync())
     out = dict(ready=rb.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
                refs=refs.download((K, 6), np.float64))
+    if trajectory is not None and trajectory is not False:
+        out.update(tj.result(tib.download((K,), np.int64)))
     if calibration is not None:
         out["calibrated"] = np.asarray(calibration["calibrated"], bool).copy()
     return out
@@ -620,7 +673,7 @@ def wire_events(frames, stream=None, frame_rows=False, phase1=False):
 
 
 def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_rows=True, calibration=None,
-                     n_cal=100):
+                     n_cal=100, trajectory=False):
     """A whole client session from the clients' wire frames, on the device end to end (KFS/Server.cpp's
     recv'd frames -> Parser.cpp:28-72): pekf_wire_events_ext_dev (the server's parse into FP64 event
     planes), pekf_frontend_init_ext_dev (phase 2) and pekf_live_ext_dev (phase 3 + the filter) on the
@@ -634,7 +687,9 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     phase-1 messages (pekf_wire_events_p1_dev), pekf_magcal_dev fits each phone's first n_cal of them wherever
     they sit in its stream, and pekf_magcal_apply_dev corrects the whole of phases 2 and 3; the returned dict
     then also has calibration, the dict calibrate_magnetometer returns.  The only host round trip is
-    wire_events' own (the error word and the bounds).  Raises ValueError, before anything is launched, if
+    wire_events' own (the error word and the bounds).  trajectory: as run_session (True: a row per three of
+    the phase-3 rows the launch reads), from the same launch, with either kind of rows and any calibration.
+    Raises ValueError, before anything is launched, if
     filters.batch is not the frames' phone count or calibration is another string."""
     K = filters.batch
     from_frames = isinstance(calibration, str)
@@ -659,10 +714,14 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     ev3 = w["ev3"]
     if w["ev3_from"]:  # (frame rows) the leading rows no phone has a phase-3 message in
         ev3 = types.SimpleNamespace(ptr=ev3.ptr + 32 * K * w["ev3_from"])
-    filters.run_events_async(ev3, w["E3"], ib, tib, cnt, refs, alpha, stream, flags=EV_F64_EVENTS)
+    tj = _Trajectory(trajectory, w["E3"], K, stream)
+    filters.run_events_async(ev3, w["E3"], ib, tib, cnt, refs, alpha, stream, flags=EV_F64_EVENTS, traj=tj.traj,
+                             traj_dt=tj.dt, traj_rows=tj.rows)
     check(lib.pekf_device_sync() if stream is None else lib.pekf_stream_sync(stream))
     out = dict(ready=rb.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
                refs=refs.download((K, 6), np.float64))
+    if trajectory is not None and trajectory is not False:
+        out.update(tj.result(tib.download((K,), np.int64)))
     if from_frames:
         calibration = out["calibration"] = _calibration_result(K, calibration)
     if calibration is not None:
@@ -770,17 +829,33 @@ class BatchedEKF:
             return tb.download((n_steps, self.batch, 4), np.float64)
         return None
 
-    def run_events_async(self, ev_planes, n_events, init, t_init, counts, refs, alpha=0.1, stream=None, flags=0):
+    def run_events_async(self, ev_planes, n_events, init, t_init, counts, refs, alpha=0.1, stream=None, flags=0,
+                         traj=None, traj_dt=None, traj_rows=0):
         """Enqueue pekf_live_ext_dev: device event planes [n_events][batch][4] f32 (synth.pack_events), init
         (batch, 6), t_init (batch,) int64; counts (batch,) int32 and refs (batch, 6) outputs -- DeviceBuffers;
-        flags: EV_TIME_EVENTS if the planes hold time events, EV_F32_RECORDS for f32 records."""
+        flags: EV_TIME_EVENTS if the planes hold time events, EV_F32_RECORDS for f32 records.
+        traj_rows > 0: pekf_live_traj_dev instead, each filter's X after its r-th record (r < traj_rows) into
+        traj, a DeviceBuffer [traj_rows][batch][4] float64, and its dt in ns into traj_dt [traj_rows][batch]
+        (optional); rows a filter does not reach are not written."""
         if self.layout != "aos" or self.flags & RUN_MIXED_PRECISION:
             raise ValueError("the fused front-end + filter kernel runs the FP64 filter on AoS state")
-        check(lib.pekf_live_ext_dev(self.batch, int(n_events), ev_planes.ptr, init.ptr, t_init.ptr, float(alpha),
-                                    self.X.ptr, self.P.ptr, self.q, self.r, counts.ptr, refs.ptr, int(flags), None,
-                                    stream))
+        traj_rows = int(traj_rows)
+        if traj_rows < 0:
+            raise ValueError("traj_rows must be >= 0")
+        if traj_rows == 0:
+            check(lib.pekf_live_ext_dev(self.batch, int(n_events), ev_planes.ptr, init.ptr, t_init.ptr, float(alpha),
+                                        self.X.ptr, self.P.ptr, self.q, self.r, counts.ptr, refs.ptr, int(flags), None,
+                                        stream))
+            return
+        if traj is None or traj.nbytes < 32 * traj_rows * self.batch:
+            raise ValueError("traj must be a DeviceBuffer of traj_rows * batch * 32 bytes")
+        if traj_dt is not None and traj_dt.nbytes < 8 * traj_rows * self.batch:
+            raise ValueError("traj_dt must be a DeviceBuffer of traj_rows * batch * 8 bytes")
+        check(lib.pekf_live_traj_dev(self.batch, int(n_events), ev_planes.ptr, init.ptr, t_init.ptr, float(alpha),
+                                     self.X.ptr, self.P.ptr, self.q, self.r, counts.ptr, refs.ptr, int(flags),
+                                     traj.ptr, traj_dt.ptr if traj_dt is not None else None, traj_rows, None, stream))
 
-    def run_events(self, ev, alpha=0.1, records="f64", events="f32"):
+    def run_events(self, ev, alpha=0.1, records="f64", events="f32", trajectory=False):
         """Raw phone events (synth.generate_events layout) -> front-end -> filter, fused in one launch
         (pekf_live_ext_dev).  Returns (counts (batch,) int32 records applied, refs (batch, 6)
         the filters' acc0 / mag0).  Any event gap and any record dt is applied (time events, escapes).
@@ -789,16 +864,24 @@ class BatchedEKF:
         result equal run_frontend + run bit for bit.
         events: "f32" the float32 samples (16 B events); "f64" the server's own values (32 B events,
         server_event_values: what std::stod parses from the phone's text), every record field FP64 --
-        equal to run_frontend(events="f64") + run bit for bit."""
+        equal to run_frontend(events="f64") + run bit for bit.
+        trajectory: True or a row cap (True: n_events // 3) adds a third value, run_session's dict of
+        trajectory (R, batch, 4), record_dt_ns (R, batch) and record_times_ns (R, batch): a pose per record,
+        from the same launch."""
         assert np.asarray(ev["types"]).shape[1] == self.batch
         evb, E, flags = _event_planes(ev, events)
         init = DeviceBuffer(48 * self.batch).upload(
             np.concatenate([ev["init_acc"], ev["init_mag"]], axis=1).astype(np.float64))
         tib = DeviceBuffer(8 * self.batch).upload(np.ascontiguousarray(ev["t_init"], np.int64))
         cnt, refs = DeviceBuffer(4 * self.batch), DeviceBuffer(48 * self.batch)
-        self.run_events_async(evb, E, init, tib, cnt, refs, alpha, flags=flags | _record_flags(records, events))
+        tj = _Trajectory(trajectory, E, self.batch)
+        self.run_events_async(evb, E, init, tib, cnt, refs, alpha, flags=flags | _record_flags(records, events),
+                              traj=tj.traj, traj_dt=tj.dt, traj_rows=tj.rows)
         check(lib.pekf_device_sync())
-        return cnt.download((self.batch,), np.int32), refs.download((self.batch, 6), np.float64)
+        out = cnt.download((self.batch,), np.int32), refs.download((self.batch, 6), np.float64)
+        if trajectory is not None and trajectory is not False:
+            out += (tj.result(ev["t_init"]),)
+        return out
 
 
 class FilterHandle:
