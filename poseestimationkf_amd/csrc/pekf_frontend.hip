@@ -126,13 +126,8 @@ __global__ __launch_bounds__(64) void k_frontend(int64_t batch, int64_t n_events
         bool esc = false;
         RecT rc{};
         if (has) {
-            if constexpr (EV64) {
-                rc.gd = fe.emit64();
-                rc.am = make_double4(fe.lpf_acc.x, fe.lpf_acc.y, fe.lpf_acc.z, fe.lpf_mag.x);
-                rc.my = make_double2(fe.lpf_mag.y, fe.lpf_mag.z);
-            } else {
-                rc = fe.emit(esc);
-            }
+            fe.pend = false;
+            rc = fe.template finish<RecT>(fe.p, esc);
         }
         const bool live = has && ready;
         if (live && esc) bad |= dtx ? 4 : 1;

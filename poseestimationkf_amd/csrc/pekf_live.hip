@@ -6,7 +6,8 @@
 // touch memory.  A record's acc / mag stay the FP64 low-pass outputs (the server's filter input,
 // KFS/KalmanFilter.cpp:279-303) in a 5-deep queue (20 KB per wave); PEKF_EV_F32_RECORDS rounds them to
 // the f32 stream record in a 6-deep queue instead (18 KB) and then equals the split pipeline bit for
-// bit.  FP64 costs +1.5-1.8 % at 1M filters x 1,024 events (same-box ABBA, profiles/r5/live_q5/): the
+// bit; FP64 events queue all-FP64 records 4 deep (20 KB).  One ring, three slot layouts (pekf_live.hpp:
+// RecordQueue over SlotsLpf / SlotsF32 / SlotsF64), each fed by Phase3T::finish in its form.  FP64 costs +1.5-1.8 % at 1M filters x 1,024 events (same-box ABBA, profiles/r5/live_q5/): the
 // shallower queue runs more filter steps with fewer lanes busy.  The split pipeline -- pekf_frontend_dev writing records to the stream planes, then
 // pekf_run_dev with counts reading them back -- pays a 40 B record write that scatters into 96 B of
 // sectors (each lane's record count drifts, so a wave's stores land in 64 different rows) plus the

@@ -1,4 +1,4 @@
-// pekf_live.hpp -- k_live, the fused front-end + filter kernel, and its record queues (see pekf_live.hip,
+// pekf_live.hpp -- k_live, the fused front-end + filter kernel, and its record queue (see pekf_live.hip,
 // which instantiates the kernels without trajectory output; pekf_live_traj.hip instantiates their TRAJ twins).
 #pragma once
 #include "pekf_phase3.hpp"
@@ -46,174 +46,178 @@ namespace pekf {
 
 // A lane's records waiting for the wave's next filter step, oldest first: a ring of Q slots per lane in
 // LDS, [slot][lane] so that a wave's accesses fall in distinct banks whatever slot each lane is at.  A
-// push or pop is a few address operations and three LDS accesses.  (Held in registers -- slots as
-// separate variables, a push selecting its slot -- the queue cost 40 selects per push and registers
-// the kernel does not have: profiles/r2/live/variants/live_ab*.log.)
-// A record whose dt does not fit its dt word (PEKF_DT_ESCAPE, a pause of 2^31 ns or more) keeps its
-// float64 dt in the slot's side entry dt[slot][lane], written and read only for such a record.
+// push or pop is a few address operations and three to five 16-byte LDS accesses.  (Held in registers --
+// slots as separate variables, a push selecting its slot -- the queue cost 40 selects per push and
+// registers the kernel does not have: profiles/r2/live/variants/live_ab*.log.)
+//
+// The ring is RecordQueue; what a slot holds is one of three layouts, one per record form of
+// Phase3T::finish (In: the form pushed).  A layout states its LDS planes and their bytes, how a record is
+// stored, how a slot is loaded and becomes gy / acc / mag, and where a dt that does not fit the f32 forms'
+// dt word (PEKF_DT_ESCAPE, a pause of 2^31 ns or more) is kept: keep_dt on the push of such a record,
+// take_dt on every pop (the record's dt in ns; has: a record was queued).
+
+// The f32 stream record (PEKF_EV_F32_RECORDS: what pekf_frontend_dev writes), 48 B per slot: the 40 B
+// record and an escaped-dt plane dt[slot][lane], written and read only for an escaped record; 6 slots
+// are 18 KB per wave.
 template <int Q>
-struct LdsQueue {
+struct SlotsF32 {
+    using In = Rec;
+    using Slot = Rec;
     static constexpr size_t kBytes = (sizeof(float4) * 2 + sizeof(float2) + sizeof(double)) * Q * kRunBlock;
     float4 (*gd)[kRunBlock];
     float4 (*am)[kRunBlock];
     float2 (*my)[kRunBlock];
     double (*dt)[kRunBlock];
-    int head = 0, n = 0;
     __device__ __forceinline__ void bind(unsigned char *lds) {
         gd = reinterpret_cast<float4(*)[kRunBlock]>(lds);
         am = reinterpret_cast<float4(*)[kRunBlock]>(lds + sizeof(float4) * Q * kRunBlock);
         dt = reinterpret_cast<double(*)[kRunBlock]>(lds + 2 * sizeof(float4) * Q * kRunBlock);
         my = reinterpret_cast<float2(*)[kRunBlock]>(lds + (2 * sizeof(float4) + sizeof(double)) * Q * kRunBlock);
     }
-    __device__ __forceinline__ int tail() const { return head + n < Q ? head + n : head + n - Q; }
-    __device__ __forceinline__ bool esc_queued() const { return false; }  // escaped dts live in the dt plane
-    __device__ __forceinline__ void push(const Rec &r, bool esc, double dtv) {
-        const int slot = tail();
+    __device__ __forceinline__ void store(int slot, const In &r) {
         gd[slot][threadIdx.x] = r.gd;
         am[slot][threadIdx.x] = r.am;
         my[slot][threadIdx.x] = r.my;
-        if (esc) dt[slot][threadIdx.x] = dtv;
-        ++n;
     }
-    using Slot = Rec;
-    // the oldest record and its dt in ns
-    __device__ __forceinline__ Slot pop(double &dtv) {
-        const Rec r = {gd[head][threadIdx.x], am[head][threadIdx.x], my[head][threadIdx.x]};
-        const uint32_t word = __float_as_uint(r.gd.w) & PEKF_DT_MASK;
-        dtv = (double)word;
-        if (word == PEKF_DT_ESCAPE) dtv = dt[head][threadIdx.x];
-        if (n > 0) {
-            head = head + 1 < Q ? head + 1 : 0;
-            --n;
-        }
-        return r;
+    __device__ __forceinline__ Slot load(int slot) const {
+        return {gd[slot][threadIdx.x], am[slot][threadIdx.x], my[slot][threadIdx.x]};
     }
-    static __device__ __forceinline__ void unpack(const Slot &r, double (&gy)[3], double (&acc)[3], double (&mag)[3]) {
+    static __device__ __forceinline__ void unpack(const Slot &r, double *gy, double *acc, double *mag) {
         gy[0] = r.gd.x; gy[1] = r.gd.y; gy[2] = r.gd.z;
         acc[0] = r.am.x; acc[1] = r.am.y; acc[2] = r.am.z;
         mag[0] = r.am.w; mag[1] = r.my.x; mag[2] = r.my.y;
     }
-    // the popped record's acc / mag again (it stays in its slot, the one before head, until a later push)
-    __device__ __forceinline__ void reload(double *a, double *m) const {
-        const int slot = head == 0 ? Q - 1 : head - 1;
-        const float4 va = am[slot][threadIdx.x];
-        const float2 vm = my[slot][threadIdx.x];
-        a[0] = va.x; a[1] = va.y; a[2] = va.z;
-        m[0] = va.w; m[1] = vm.x; m[2] = vm.y;
+    __device__ __forceinline__ bool esc_queued() const { return false; }  // escaped dts live in the dt plane
+    __device__ __forceinline__ void keep_dt(int slot, double dtv) { dt[slot][threadIdx.x] = dtv; }
+    __device__ __forceinline__ double take_dt(int slot, const Slot &r, bool) {
+        const uint32_t word = __float_as_uint(r.gd.w) & PEKF_DT_MASK;
+        double dtv = (double)word;
+        if (word == PEKF_DT_ESCAPE) dtv = dt[slot][threadIdx.x];
+        return dtv;
     }
 };
 
-// The queue with FP64 acc / mag: what the server's filter receives (KFS/KalmanFilter.cpp:279-303 hands
-// the double low-pass outputs to Prediction / Correction), not the f32 stream record.  Per slot the
+// The f32 gyro / dt word with FP64 acc / mag: what the server's filter receives (KFS/KalmanFilter.cpp:279-303
+// hands the double low-pass outputs to Prediction / Correction), not the f32 stream record.  Per slot the
 // gyro / dt word (16 B) and acc and mag as three double2 planes (48 B): 5 slots x 64 B x 64 lanes is
 // 20 KB per wave, exactly the CU's 160 KB at 2 waves per SIMD, so there is no room for an escaped-dt
-// plane.  A record whose dt does not fit the dt word keeps its float64 dt in a register instead
-// (esc_dt), one per lane: k_live steps a wave while any lane still has such a record queued, so a lane
-// never holds two (escapes are pauses of 2.1 s or more: rare, and cheap to drain for).
+// plane.  An escaped record keeps its float64 dt in a register instead (esc_dt), one per lane: k_live
+// steps a wave while any lane still has such a record queued (want_step) and completes at most one
+// record per lane and block (its kPush == 1 static_assert), so a lane never holds two (escapes are pauses
+// of 2.1 s or more: rare, and cheap to drain for).
 template <int Q>
-struct LdsQueue64 {
-    static constexpr size_t kBytes = (sizeof(float4) + 3 * sizeof(double2)) * Q * kRunBlock;
-    float4 (*gd)[kRunBlock];
-    double2 (*am)[3][kRunBlock];  // {acc.x, acc.y}, {acc.z, mag.x}, {mag.y, mag.z}
-    double esc_dt = __builtin_nan("");  // the queued escaped record's dt (NaN: none queued)
-    int head = 0, n = 0;
-    __device__ __forceinline__ void bind(unsigned char *lds) {
-        am = reinterpret_cast<double2(*)[3][kRunBlock]>(lds);
-        gd = reinterpret_cast<float4(*)[kRunBlock]>(lds + 3 * sizeof(double2) * Q * kRunBlock);
-    }
-    // a lane has an escaped record queued (k_live then steps until it is applied)
-    __device__ __forceinline__ bool esc_queued() const { return esc_dt == esc_dt; }
-    __device__ __forceinline__ void push(const float4 &g, const V3 &a, const V3 &m, bool esc, double dtv) {
-        const int slot = head + n < Q ? head + n : head + n - Q;
-        gd[slot][threadIdx.x] = g;
-        am[slot][0][threadIdx.x] = make_double2(a.x, a.y);
-        am[slot][1][threadIdx.x] = make_double2(a.z, m.x);
-        am[slot][2][threadIdx.x] = make_double2(m.y, m.z);
-        if (esc) esc_dt = dtv;
-        ++n;
-    }
+struct SlotsLpf {
+    using In = RecLpf;
     struct Slot {
         float4 gd;
         double2 v[3];
     };
-    __device__ __forceinline__ Slot pop(double &dtv) {
-        const Slot r = {gd[head][threadIdx.x], {am[head][0][threadIdx.x], am[head][1][threadIdx.x], am[head][2][threadIdx.x]}};
-        const uint32_t word = __float_as_uint(r.gd.w) & PEKF_DT_MASK;
-        dtv = (double)word;
-        if (n > 0 && word == PEKF_DT_ESCAPE) {
-            dtv = esc_dt;
-            esc_dt = __builtin_nan("");
-        }
-        if (n > 0) {
-            head = head + 1 < Q ? head + 1 : 0;
-            --n;
-        }
-        return r;
+    static constexpr size_t kBytes = (sizeof(float4) + 3 * sizeof(double2)) * Q * kRunBlock;
+    float4 (*gd)[kRunBlock];
+    double2 (*am)[3][kRunBlock];  // {acc.x, acc.y}, {acc.z, mag.x}, {mag.y, mag.z}
+    double esc_dt = __builtin_nan("");  // the queued escaped record's dt (NaN: none queued)
+    __device__ __forceinline__ void bind(unsigned char *lds) {
+        am = reinterpret_cast<double2(*)[3][kRunBlock]>(lds);
+        gd = reinterpret_cast<float4(*)[kRunBlock]>(lds + 3 * sizeof(double2) * Q * kRunBlock);
     }
-    static __device__ __forceinline__ void unpack(const Slot &r, double (&gy)[3], double (&acc)[3], double (&mag)[3]) {
+    __device__ __forceinline__ void store(int slot, const In &r) {
+        gd[slot][threadIdx.x] = r.gd;
+        am[slot][0][threadIdx.x] = make_double2(r.acc.x, r.acc.y);
+        am[slot][1][threadIdx.x] = make_double2(r.acc.z, r.mag.x);
+        am[slot][2][threadIdx.x] = make_double2(r.mag.y, r.mag.z);
+    }
+    __device__ __forceinline__ Slot load(int slot) const {
+        return {gd[slot][threadIdx.x], {am[slot][0][threadIdx.x], am[slot][1][threadIdx.x], am[slot][2][threadIdx.x]}};
+    }
+    static __device__ __forceinline__ void unpack(const Slot &r, double *gy, double *acc, double *mag) {
         gy[0] = r.gd.x; gy[1] = r.gd.y; gy[2] = r.gd.z;
         acc[0] = r.v[0].x; acc[1] = r.v[0].y; acc[2] = r.v[1].x;
         mag[0] = r.v[1].y; mag[1] = r.v[2].x; mag[2] = r.v[2].y;
     }
-    __device__ __forceinline__ void reload(double *a, double *m) const {
-        const int slot = head == 0 ? Q - 1 : head - 1;
-        const double2 v0 = am[slot][0][threadIdx.x], v1 = am[slot][1][threadIdx.x], v2 = am[slot][2][threadIdx.x];
-        a[0] = v0.x; a[1] = v0.y; a[2] = v1.x;
-        m[0] = v1.y; m[1] = v2.x; m[2] = v2.y;
+    // a lane has an escaped record queued (k_live then steps until it is applied)
+    __device__ __forceinline__ bool esc_queued() const { return esc_dt == esc_dt; }
+    __device__ __forceinline__ void keep_dt(int, double dtv) { esc_dt = dtv; }
+    __device__ __forceinline__ double take_dt(int, const Slot &r, bool has) {
+        const uint32_t word = __float_as_uint(r.gd.w) & PEKF_DT_MASK;
+        double dtv = (double)word;
+        if (has && word == PEKF_DT_ESCAPE) {
+            dtv = esc_dt;
+            esc_dt = __builtin_nan("");
+        }
+        return dtv;
     }
 };
 
-// The queue of FP64-event launches: every field of the record in FP64 -- gyro and dt too, as the server's
-// filter gets them (dt any float64, so no escape) -- 80 B per slot as five double2 planes [slot][lane]
-// (16 B per lane and plane: conflict-free ds_*_b128), 4 deep = 20 KB per wave, the CU's 160 KB at 2
-// waves per SIMD.
+// The all-FP64 record of FP64-event launches: gyro and dt too, as the server's filter gets them -- the dt
+// any float64, so there is no escape and nothing to keep -- 80 B per slot as five double2 planes
+// [slot][lane] (16 B per lane and plane: conflict-free ds_*_b128), 4 deep = 20 KB per wave, the CU's
+// 160 KB at 2 waves per SIMD.
 template <int Q>
-struct LdsQueueF64 {
-    static constexpr size_t kBytes = 5 * sizeof(double2) * Q * kRunBlock;
-    double2 (*v)[5][kRunBlock];  // {gx, gy}, {gz, dt}, {ax, ay}, {az, mx}, {my, mz}
-    int head = 0, n = 0;
-    __device__ __forceinline__ void bind(unsigned char *lds) { v = reinterpret_cast<double2(*)[5][kRunBlock]>(lds); }
-    __device__ __forceinline__ bool esc_queued() const { return false; }
-    __device__ __forceinline__ void push(const double4 &g, const V3 &a, const V3 &m) {
-        const int slot = head + n < Q ? head + n : head + n - Q;
-        v[slot][0][threadIdx.x] = make_double2(g.x, g.y);
-        v[slot][1][threadIdx.x] = make_double2(g.z, g.w);
-        v[slot][2][threadIdx.x] = make_double2(a.x, a.y);
-        v[slot][3][threadIdx.x] = make_double2(a.z, m.x);
-        v[slot][4][threadIdx.x] = make_double2(m.y, m.z);
-        ++n;
-    }
+struct SlotsF64 {
+    using In = Rec64;
     struct Slot {
         double2 v[5];
     };
-    __device__ __forceinline__ Slot pop(double &dtv) {
+    static constexpr size_t kBytes = 5 * sizeof(double2) * Q * kRunBlock;
+    double2 (*v)[5][kRunBlock];  // {gx, gy}, {gz, dt}, {ax, ay}, {az, mx}, {my, mz}
+    __device__ __forceinline__ void bind(unsigned char *lds) { v = reinterpret_cast<double2(*)[5][kRunBlock]>(lds); }
+    __device__ __forceinline__ void store(int slot, const In &r) {
+        v[slot][0][threadIdx.x] = make_double2(r.gd.x, r.gd.y);
+        v[slot][1][threadIdx.x] = make_double2(r.gd.z, r.gd.w);
+        v[slot][2][threadIdx.x] = make_double2(r.am.x, r.am.y);
+        v[slot][3][threadIdx.x] = make_double2(r.am.z, r.am.w);
+        v[slot][4][threadIdx.x] = r.my;
+    }
+    __device__ __forceinline__ Slot load(int slot) const {
         Slot r;
 #pragma unroll
-        for (int k = 0; k < 5; ++k) r.v[k] = v[head][k][threadIdx.x];
-        dtv = r.v[1].y;
+        for (int k = 0; k < 5; ++k) r.v[k] = v[slot][k][threadIdx.x];
+        return r;
+    }
+    static __device__ __forceinline__ void unpack(const Slot &r, double *gy, double *acc, double *mag) {
+        gy[0] = r.v[0].x; gy[1] = r.v[0].y; gy[2] = r.v[1].x;
+        acc[0] = r.v[2].x; acc[1] = r.v[2].y; acc[2] = r.v[3].x;
+        mag[0] = r.v[3].y; mag[1] = r.v[4].x; mag[2] = r.v[4].y;
+    }
+    __device__ __forceinline__ bool esc_queued() const { return false; }
+    __device__ __forceinline__ void keep_dt(int, double) {}
+    __device__ __forceinline__ double take_dt(int, const Slot &r, bool) { return r.v[1].y; }
+};
+
+// The ring over a layout's Q slots: head, the n records queued from it, the tail a push fills
+template <template <int> class Slots, int Q>
+struct RecordQueue : Slots<Q> {
+    int head = 0, n = 0;
+    __device__ __forceinline__ int tail() const { return head + n < Q ? head + n : head + n - Q; }
+    // the slot popped last: its record stays there until a later push
+    __device__ __forceinline__ int last() const { return head == 0 ? Q - 1 : head - 1; }
+    __device__ __forceinline__ void push(const typename Slots<Q>::In &r, bool esc, double dtv) {
+        const int slot = tail();
+        this->store(slot, r);
+        if (esc) this->keep_dt(slot, dtv);
+        ++n;
+    }
+    // the oldest record and its dt in ns
+    __device__ __forceinline__ typename Slots<Q>::Slot pop(double &dtv) {
+        const typename Slots<Q>::Slot r = this->load(head);
+        dtv = this->take_dt(head, r, n > 0);
         if (n > 0) {
             head = head + 1 < Q ? head + 1 : 0;
             --n;
         }
         return r;
     }
-    static __device__ __forceinline__ void unpack(const Slot &r, double (&gy)[3], double (&acc)[3], double (&mag)[3]) {
-        gy[0] = r.v[0].x; gy[1] = r.v[0].y; gy[2] = r.v[1].x;
-        acc[0] = r.v[2].x; acc[1] = r.v[2].y; acc[2] = r.v[3].x;
-        mag[0] = r.v[3].y; mag[1] = r.v[4].x; mag[2] = r.v[4].y;
-    }
+    // the popped record's acc / mag again
     __device__ __forceinline__ void reload(double *a, double *m) const {
-        const int slot = head == 0 ? Q - 1 : head - 1;
-        const double2 v2 = v[slot][2][threadIdx.x], v3 = v[slot][3][threadIdx.x], v4 = v[slot][4][threadIdx.x];
-        a[0] = v2.x; a[1] = v2.y; a[2] = v3.x;
-        m[0] = v3.y; m[1] = v4.x; m[2] = v4.y;
+        double gy[3];
+        Slots<Q>::unpack(this->load(last()), gy, a, m);
     }
 };
 
 // TE: the event planes may hold time events (Phase3::event).  R64: records keep their FP64 acc / mag
-// (LdsQueue64); otherwise they are the f32 stream records pekf_frontend_dev writes (LdsQueue).
+// (SlotsLpf); otherwise they are the f32 stream records pekf_frontend_dev writes (SlotsF32).
 // EV64: FP64 events (PEKF_EV_F64_EVENTS, double4 planes: the server's own sample values), records all
-// FP64 (LdsQueueF64); TE and R64 do not apply.
+// FP64 (SlotsF64); TE and R64 do not apply.
 // TRAJ: a pose per record (the server's X_k, Parser::ExecuteKalmanFilter, KFS/Parser.cpp:248-267): the
 // lane's r-th record of the launch (r < traj_rows) leaves its world-basis unit X in traj[r][b] (4 doubles,
 // formed by ref_to_world as k_run's trajectory row and the launch's final X are) and, with traj_dt, the dt
@@ -234,9 +238,9 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     static_assert(kRing % kFlush == 0, "the ring depth must be a multiple of the emit period");
     static_assert(kQueue >= kPush, "the queue must hold a block's records");
     static_assert(!(EV64 && (TE || R64)), "FP64 events take their own record queue and carry their times");
-    // LdsQueue64 keeps ONE escaped dt per lane (esc_dt) and want_step drains it before the next block,
+    // SlotsLpf keeps ONE escaped dt per lane (esc_dt) and want_step drains it before the next block,
     // which is safe only while a block completes at most one record per lane
-    static_assert(!R64 || kPush == 1, "LdsQueue64's single escaped-dt register needs one record per lane per block");
+    static_assert(!R64 || kPush == 1, "SlotsLpf's single escaped-dt register needs one record per lane per block");
     const int64_t b = (int64_t)blockIdx.x * kRunBlock + threadIdx.x;
     if (b >= batch) return;
 
@@ -261,8 +265,8 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     const auto Wr = enter_ref_basis<TRAJ && !kLate>(Wf, refs + 6 * b, false, x, P, rs);
     const StepK<double> kc = step_consts<double, true>(qs, rs);
 
-    using Queue = std::conditional_t<EV64, LdsQueueF64<kQueue>,
-                                     std::conditional_t<R64, LdsQueue64<kQueue>, LdsQueue<kQueue>>>;
+    using Queue = std::conditional_t<EV64, RecordQueue<SlotsF64, kQueue>,
+                                     std::conditional_t<R64, RecordQueue<SlotsLpf, kQueue>, RecordQueue<SlotsF32, kQueue>>>;
     __shared__ __attribute__((aligned(16))) unsigned char q_lds[Queue::kBytes];
     Queue queue;
     queue.bind(q_lds);
@@ -300,19 +304,11 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
         }
         mode.leave();
     };
-    // the pending record (captured by Phase3::event) into the queue
+    // the pending record (captured by Phase3::event), finished in the queue's form, into the queue
     auto push_pending = [&](const auto &q) {
         bool esc;
-        if constexpr (EV64) {
-            const double4 g = fe.emit64(q);
-            if (ready) queue.push(g, fe.lpf_acc, fe.lpf_mag);
-        } else if constexpr (R64) {
-            const float4 g = fe.emit_lpf(q, esc);
-            if (ready) queue.push(g, fe.lpf_acc, fe.lpf_mag, esc, q.dt);
-        } else {
-            const Rec rc = fe.emit(q, esc);
-            if (ready) queue.push(rc, esc, q.dt);
-        }
+        const auto rc = fe.template finish<typename Queue::In>(q, esc);
+        if (ready) queue.push(rc, esc, q.dt);
     };
     auto flush = [&]() {
         if (fe.pend) {

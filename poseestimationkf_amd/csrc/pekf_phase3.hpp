@@ -8,8 +8,9 @@
 // normalised (:221-228), low-pass filtered (alpha, from a zero state: KalmanFilter.cpp:16-18,21-24,
 // 279-303), dt = gyro time - the previous record's (KalmanFilter.cpp:306-308).  FP64 arithmetic (one
 // reciprocal / rsqrt with a Newton step instead of IEEE divisions: ~1e-15 relative).  Records for the
-// stream planes are rounded to f32 like every record of the stream (emit); k_live can take the low-pass
-// outputs in FP64 instead (emit_lpf + lpf_acc / lpf_mag), as the server hands them to its filter.  The arithmetic is contracted as the compiler's default
+// stream planes are rounded to f32 like every record of the stream (Rec); k_live can take the low-pass
+// outputs in FP64 instead (RecLpf), as the server hands them to its filter; FP64 events make all-FP64
+// records (Rec64): Phase3T::finish makes all three.  The arithmetic is contracted as the compiler's default
 // (fp contract fast) whatever the including file is compiled with: every function with arithmetic
 // opens with that pragma, so k_live's records are k_frontend's.
 //
@@ -52,6 +53,12 @@ struct V3 {
 struct F3 {
     float x, y, z;
 };
+// The f32 stream record's gyro / dt half with acc / mag left in FP64 (one of Phase3T::finish's three forms;
+// Rec and Rec64 are the stream planes' records, pekf_internal.hpp)
+struct RecLpf {
+    float4 gd;
+    V3 acc, mag;
+};
 __device__ __forceinline__ V3 widen(const F3 &f) { return {f.x, f.y, f.z}; }
 __device__ __forceinline__ V3 widen(const V3 &v) { return v; }
 // component-wise c ? a : b (a struct-valued ?: would go through scratch memory)
@@ -77,7 +84,7 @@ __device__ __forceinline__ V3 normalised_fma(const V3 &v) {
 }
 
 // A completed record's inputs, captured when the state machine completes it (its state moves on at
-// once) and turned into the record by Phase3::emit: the gyro sample, acc_0 / acc_1 / mag_0 / mag_1
+// once) and turned into the record by Phase3::finish: the gyro sample, acc_0 / acc_1 / mag_0 / mag_1
 // (f32 samples; *_mean: acc_0 / mag_0 is still the phase-2 mean) and the time differences of
 // LinearInterpolationSensor and of the record's dt.
 template <typename S>
@@ -398,7 +405,8 @@ struct Phase3T {
         mag1_set = m1s && !done;
     }
 
-    // the deferring form: the completed record's inputs wait in p (pend) for emit(esc)
+    // the deferring form: the completed record's inputs wait in p (pend) for finish; an escaped record's
+    // float64 dt stays in p.dt
     template <bool TE = false>
     __device__ __forceinline__ void event(const float4 v4) {
         event<TE>(v4, [&](const Raw &r) {
@@ -411,16 +419,6 @@ struct Phase3T {
             pend = true;
             p = r;
         });
-    }
-    // the pending record; its dt stays in p.dt (the float64 an escaped record needs)
-    __device__ __forceinline__ Rec emit(bool &esc) {
-        pend = false;
-        return emit(p, esc);
-    }
-    // the same with the low-pass outputs left in FP64 (lpf_acc / lpf_mag)
-    __device__ __forceinline__ float4 emit_lpf(bool &esc) {
-        pend = false;
-        return emit_lpf(p, esc);
     }
 
     // The low-pass step l <- alpha x + beta l (KalmanFilter.cpp:285,298), rounded as fma(beta, l, alpha x)
@@ -454,37 +452,38 @@ struct Phase3T {
         lpf_step(lpf_acc.x, a.x); lpf_step(lpf_acc.y, a.y); lpf_step(lpf_acc.z, a.z);
     }
 
-    // lpf_record, and the gyro / dt half of the 40 B record, which is returned (f32 events).
-    // esc: its dt does not fit the dt word (not in [0, 2^31 - 1) ns): the word is PEKF_DT_ESCAPE and
-    // the caller keeps q.dt beside the record (pekf.h).
-    __device__ __forceinline__ float4 emit_lpf(const Raw &q, bool &esc) {
-        lpf_record(q);
-        esc = !(q.dt >= 0.0 && q.dt < (double)PEKF_DT_ESCAPE);
-        return make_float4((float)q.gyro.x, (float)q.gyro.y, (float)q.gyro.z,
-                           __uint_as_float(esc ? PEKF_DT_ESCAPE : (uint32_t)q.dt));
-    }
-
-    // lpf_record, and the record's gyro and dt in FP64 (FP64 events: {gx, gy, gz, dt_ns}, the GD half of
-    // an 80 B record; the dt is any float64, so nothing is escaped).
-    __device__ __forceinline__ double4 emit64(const Raw &q) {
-        static_assert(kLean, "FP64 records come from FP64 events");
-        // the captured interpolations normalised (their scale d drops out), then the low-pass
-        const V3 a = normalised_fma(q.A), m = normalised_fma(q.M);
-        lpf_step(lpf_mag.x, m.x); lpf_step(lpf_mag.y, m.y); lpf_step(lpf_mag.z, m.z);
-        lpf_step(lpf_acc.x, a.x); lpf_step(lpf_acc.y, a.y); lpf_step(lpf_acc.z, a.z);
-        return make_double4(q.gyro.x, q.gyro.y, q.gyro.z, q.dt);
-    }
-    __device__ __forceinline__ double4 emit64() {
-        pend = false;
-        return emit64(p);
-    }
-
-    // The 40 B stream record (acc / mag rounded to f32, as every record of the stream planes).
-    __device__ __forceinline__ Rec emit(const Raw &q, bool &esc) {
-        Rec r;
-        r.gd = emit_lpf(q, esc);
-        r.am = make_float4((float)lpf_acc.x, (float)lpf_acc.y, (float)lpf_acc.z, (float)lpf_mag.x);
-        r.my = make_float2((float)lpf_mag.y, (float)lpf_mag.z);
+    // The one way a captured record is finished -- lpf_record (FP64 events: the captured interpolations
+    // normalised, their scale d dropping out, then the low-pass) -- and handed on in the form R asks for:
+    //   Rec     the 40 B stream record (acc / mag rounded to f32, as every record of the stream planes);
+    //   RecLpf  its gyro / dt half with the low-pass outputs left in FP64;
+    //   Rec64   every field FP64 ({gx, gy, gz, dt_ns}, ...), which FP64 events make and only they.
+    // esc: the dt does not fit the f32 forms' dt word (not in [0, 2^31 - 1) ns), the word is PEKF_DT_ESCAPE
+    // and the caller keeps q.dt, a float64, beside the record (pekf.h).  Rec64's dt is any float64, so
+    // nothing is escaped.  The caller clears pend.
+    template <typename R>
+    __device__ __forceinline__ R finish(const Raw &q, bool &esc) {
+        static_assert(std::is_same<R, Rec64>::value == kLean, "FP64 events make FP64 records, f32 events the others");
+        R r;
+        esc = false;
+        if constexpr (kLean) {
+            const V3 a = normalised_fma(q.A), m = normalised_fma(q.M);
+            lpf_step(lpf_mag.x, m.x); lpf_step(lpf_mag.y, m.y); lpf_step(lpf_mag.z, m.z);
+            lpf_step(lpf_acc.x, a.x); lpf_step(lpf_acc.y, a.y); lpf_step(lpf_acc.z, a.z);
+            r.gd = make_double4(q.gyro.x, q.gyro.y, q.gyro.z, q.dt);
+        } else {
+            lpf_record(q);
+            esc = !(q.dt >= 0.0 && q.dt < (double)PEKF_DT_ESCAPE);
+            r.gd = make_float4((float)q.gyro.x, (float)q.gyro.y, (float)q.gyro.z,
+                               __uint_as_float(esc ? PEKF_DT_ESCAPE : (uint32_t)q.dt));
+        }
+        if constexpr (std::is_same<R, RecLpf>::value) {
+            r.acc = lpf_acc;
+            r.mag = lpf_mag;
+        } else {
+            using T = decltype(r.my.x);
+            r.am = decltype(r.am)((T)lpf_acc.x, (T)lpf_acc.y, (T)lpf_acc.z, (T)lpf_mag.x);
+            r.my = decltype(r.my)((T)lpf_mag.y, (T)lpf_mag.z);
+        }
         return r;
     }
 };

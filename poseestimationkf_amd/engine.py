@@ -144,40 +144,89 @@ def read_log_records(path):
 
 # ------------------------------------------------------------------ resident IMU window
 
-class IMUWindow:
+def _stack_ragged(cols, lens, n_records=None):
+    """Filters of different lengths side by side: cols[k] (lens[k], ...) -> ((n, K, ...) zero-padded, counts (K,)
+    int32 each filter's own rows), n the longest or n_records."""
+    n = int(max(lens)) if n_records is None else int(n_records)
+    out = np.zeros((n, len(cols)) + cols[0].shape[1:], cols[0].dtype)
+    for k, c in enumerate(cols):
+        m = min(n, c.shape[0])
+        out[:m, k] = c[:m]
+    return out, np.minimum(np.asarray(lens, np.int64), n).astype(np.int32)
+
+
+class _RecordWindow:
+    """What the two resident windows share: `window` steps x `batch` filters as three planes [window][batch] of
+    4 / 4 / 2 scalars of _DTYPE (gd, am, my; filter-minor), the per-filter reference block refs (batch, 6)
+    float64, the ragged counts, and the side outputs of the entries _WAHBA / _GYRO."""
+    _DTYPE = _WAHBA = _GYRO = None
+
+    def __init__(self, batch, window):
+        self.batch, self.window = int(batch), int(window)
+        n = self.batch * self.window * np.dtype(self._DTYPE).itemsize
+        self.gd = DeviceBuffer(4 * n)
+        self.am = DeviceBuffer(4 * n)
+        self.my = DeviceBuffer(2 * n)
+        self.refs = DeviceBuffer(48 * self.batch)
+        self.counts = None  # per-filter valid record counts when filters are ragged (logs, front-end)
+
+    @property
+    def nbytes(self):
+        return self.gd.nbytes + self.am.nbytes + self.my.nbytes
+
+    def _dtx_arg(self):
+        """the entry's dt side plane argument, for the window that has one"""
+        return ()
+
+    def _download(self, cols):
+        """(gd, am, my, refs) of filter columns `cols`"""
+        gd, am, my = (b.download((self.window, self.batch, k), self._DTYPE)[:, cols]
+                      for b, k in ((self.gd, 4), (self.am, 4), (self.my, 2)))
+        return gd, am, my, self.refs.download((self.batch, 6), np.float64)[cols]
+
+    def wahba_quaternions(self, n_steps=None, step0=0, k_acc=0.5, k_mag=0.5):
+        """Pure-Wahba attitude of every record with fixed weights (main_file.py:40): (n_steps, batch, 4)."""
+        n_steps = self.window if n_steps is None else int(n_steps)
+        out = DeviceBuffer(32 * n_steps * self.batch)
+        check(getattr(lib, self._WAHBA)(self.batch, n_steps, self.window, int(step0), self.am.ptr, self.my.ptr,
+                                        self.refs.ptr, float(k_acc), float(k_mag), out.ptr, None))
+        check(lib.pekf_device_sync())
+        return out.download((n_steps, self.batch, 4), np.float64)
+
+    def gyro_chain(self, q0=None, n_steps=None, step0=0, want_traj=False):
+        """Pure-gyro attitude (RK4 of the gyro records alone, KFS/KalmanFilter.cpp:149) from q0 (default
+        [1,0,0,0]); returns (q_final (batch,4), traj (n_steps,batch,4) or None)."""
+        n_steps = self.window if n_steps is None else int(n_steps)
+        q = np.tile([1.0, 0.0, 0.0, 0.0], (self.batch, 1)) if q0 is None else f64(q0, (self.batch, 4))
+        qb = DeviceBuffer(32 * self.batch).upload(q)
+        tb = DeviceBuffer(32 * n_steps * self.batch) if want_traj else None
+        check(getattr(lib, self._GYRO)(self.batch, n_steps, self.window, int(step0), self.gd.ptr, *self._dtx_arg(),
+                                       qb.ptr, tb.ptr if tb is not None else None, None))
+        check(lib.pekf_device_sync())
+        return (qb.download((self.batch, 4), np.float64),
+                tb.download((n_steps, self.batch, 4), np.float64) if want_traj else None)
+
+
+class IMUWindow(_RecordWindow):
     """`window` steps x `batch` filters of the 40 B/step input record, resident in HBM.
 
     Planes (filter-minor, see synth.pack_planes): gd float4, am float4, my float2, plus the
     per-filter reference block refs (batch, 6) float64.  Either uploaded from host records or
     generated on the device with the bit-identical Philox generator (pekf_synth_dev).
     """
+    _DTYPE, _WAHBA, _GYRO = np.float32, "pekf_wahba_stream_dev", "pekf_gyro_chain_ext_dev"
 
     def __init__(self, batch, window):
-        self.batch, self.window = int(batch), int(window)
-        n = self.batch * self.window
-        self.gd = DeviceBuffer(16 * n)
-        self.am = DeviceBuffer(16 * n)
-        self.my = DeviceBuffer(8 * n)
-        self.refs = DeviceBuffer(48 * self.batch)
-        self.counts = None  # per-filter valid record counts when filters are ragged (logs, front-end)
+        super().__init__(batch, window)
         self.dtx = None     # dt side plane [window][batch] float64 when some record's dt is escaped (pekf.h)
 
-    @property
-    def nbytes(self):
-        return self.gd.nbytes + self.am.nbytes + self.my.nbytes
+    def _dtx_arg(self):
+        # escaped records (a dt the word cannot hold) take their dt from the side plane, as in the filter
+        return (self.dtx.ptr if self.dtx is not None else None,)
 
     @classmethod
     def from_records(cls, rec: synth.Records):
-        W, K = rec.dtw.shape
-        win = cls(K, W)
-        gd, am, my = synth.pack_planes(rec)
-        win.gd.upload(gd)
-        win.am.upload(am)
-        win.my.upload(my)
-        win.refs.upload(synth.refs_array(rec.acc0, rec.mag0))
-        if rec.dtx is not None:
-            win.dtx = DeviceBuffer(8 * W * K).upload(np.ascontiguousarray(rec.dtx, np.float64))
-        return win
+        return cls.from_planes(*synth.pack_planes(rec), rec.acc0, rec.mag0, rec.dtx)
 
     @classmethod
     def from_planes(cls, gd, am, my, acc0, mag0, dtx=None):
@@ -199,27 +248,17 @@ class IMUWindow:
         it), shorter logs are zero-padded and win.counts[b] is filter b's own record count,
         which BatchedEKF.run applies so each filter consumes exactly its own records."""
         recs = [read_log_records(p) for p in paths]
-        lens = np.array([r.dtw.shape[0] for r in recs], dtype=np.int64)
-        n = int(lens.max()) if n_records is None else int(n_records)
+        lens = [r.dtw.shape[0] for r in recs]
 
-        def cat(name):
-            out = []
-            for r in recs:
-                a = getattr(r, name)
-                m = min(n, a.shape[0])
-                pad = np.zeros((n,) + a.shape[1:], a.dtype)
-                pad[:m] = a[:m]
-                out.append(pad)
-            return np.concatenate(out, axis=1)
-        escaped = any(r.dtx is not None for r in recs)
-        dtx = None
-        if escaped:  # logs without escapes get a zero side plane (never read: their words are not escapes)
-            dtx = [r.dtx if r.dtx is not None else np.zeros(r.dtw.shape, np.float64) for r in recs]
-            dtx = np.concatenate([np.pad(d[:n], ((0, n - min(n, d.shape[0])), (0, 0))) for d in dtx], axis=1)
-        rec = synth.Records(cat("gyro"), cat("acc"), cat("mag"), cat("dtw"),
+        def cat(name):  # logs without escapes get a zero side plane (never read: their words are not escapes)
+            cols = [getattr(r, name) if getattr(r, name) is not None else np.zeros(r.dtw.shape) for r in recs]
+            return _stack_ragged([c[:, 0] for c in cols], lens, n_records)
+        dtx = cat("dtx")[0] if any(r.dtx is not None for r in recs) else None
+        dtw, counts = cat("dtw")
+        rec = synth.Records(cat("gyro")[0], cat("acc")[0], cat("mag")[0], dtw,
                             np.concatenate([r.acc0 for r in recs]), np.concatenate([r.mag0 for r in recs]), dtx)
         win = cls.from_records(rec)
-        win.counts = np.minimum(lens, n).astype(np.int32)
+        win.counts = counts
         return win
 
     def synthesize(self, seed=synth.DEFAULT_SEED, first_filter=0, missing=False,
@@ -232,42 +271,15 @@ class IMUWindow:
             check(lib.pekf_device_sync())
         return self
 
-    def wahba_quaternions(self, n_steps=None, step0=0, k_acc=0.5, k_mag=0.5):
-        """Pure-Wahba attitude of every record with fixed weights (main_file.py:40): (n_steps, batch, 4)."""
-        n_steps = self.window if n_steps is None else int(n_steps)
-        out = DeviceBuffer(32 * n_steps * self.batch)
-        check(lib.pekf_wahba_stream_dev(self.batch, n_steps, self.window, int(step0), self.am.ptr, self.my.ptr,
-                                        self.refs.ptr, float(k_acc), float(k_mag), out.ptr, None))
-        check(lib.pekf_device_sync())
-        return out.download((n_steps, self.batch, 4), np.float64)
-
-    def gyro_chain(self, q0=None, n_steps=None, step0=0, want_traj=False):
-        """Pure-gyro attitude (RK4 of the gyro records alone, KFS/KalmanFilter.cpp:149) from q0 (default
-        [1,0,0,0]); returns (q_final (batch,4), traj (n_steps,batch,4) or None)."""
-        n_steps = self.window if n_steps is None else int(n_steps)
-        q = np.tile([1.0, 0.0, 0.0, 0.0], (self.batch, 1)) if q0 is None else f64(q0, (self.batch, 4))
-        qb = DeviceBuffer(32 * self.batch).upload(q)
-        tb = DeviceBuffer(32 * n_steps * self.batch) if want_traj else None
-        # escaped records (a dt the word cannot hold) take their dt from the window's side plane, as in the filter
-        check(lib.pekf_gyro_chain_ext_dev(self.batch, n_steps, self.window, int(step0), self.gd.ptr,
-                                          self.dtx.ptr if self.dtx is not None else None, qb.ptr,
-                                          tb.ptr if tb is not None else None, None))
-        check(lib.pekf_device_sync())
-        return (qb.download((self.batch, 4), np.float64),
-                tb.download((n_steps, self.batch, 4), np.float64) if want_traj else None)
-
     def download_filters(self, cols):
         """Pull the records of filter columns `cols` back to the host as synth.Records."""
         cols = np.asarray(cols)
-        gd = self.gd.download((self.window, self.batch, 4), np.float32)[:, cols]
-        am = self.am.download((self.window, self.batch, 4), np.float32)[:, cols]
-        my = self.my.download((self.window, self.batch, 2), np.float32)[:, cols]
-        refs = self.refs.download((self.batch, 6), np.float64)[cols]
+        gd, am, my, refs = self._download(cols)
         dtx = None if self.dtx is None else self.dtx.download((self.window, self.batch), np.float64)[:, cols]
         return synth.unpack_planes(gd, am, my, refs[:, :3], refs[:, 3:], dtx)
 
 
-class RecordWindow64:
+class RecordWindow64(_RecordWindow):
     """`window` steps x `batch` filters of FP64 records (80 B per filter-record, pekf_run_rec64_dev), for
     inputs that are float64 to begin with: recorded logs, parsed into float64 as the reference parses
     them (ReadFile.py:14-21), where IMUWindow's 40 B record would round them to f32.
@@ -276,19 +288,7 @@ class RecordWindow64:
     {mag yz}; dt is the float64 T - previousT itself (any pause, clock step or fraction).  Every record
     is a full record (no missing-magnetometer flag).  BatchedEKF.run / run_async take it like an
     IMUWindow (FP64 AoS state)."""
-
-    def __init__(self, batch, window):
-        self.batch, self.window = int(batch), int(window)
-        n = self.batch * self.window
-        self.gd = DeviceBuffer(32 * n)
-        self.am = DeviceBuffer(32 * n)
-        self.my = DeviceBuffer(16 * n)
-        self.refs = DeviceBuffer(48 * self.batch)
-        self.counts = None  # per-filter valid record counts when filters are ragged (logs)
-
-    @property
-    def nbytes(self):
-        return self.gd.nbytes + self.am.nbytes + self.my.nbytes
+    _DTYPE, _WAHBA, _GYRO = np.float64, "pekf_wahba_stream_rec64_dev", "pekf_gyro_chain_rec64_dev"
 
     @classmethod
     def from_arrays(cls, gyro, dt_ns, acc, mag, acc0, mag0):
@@ -320,51 +320,17 @@ class RecordWindow64:
             check(lib.pekf_log_read64(bpath, n.value, g.ctypes.data, a.ctypes.data, m.ctypes.data, dt.ctypes.data,
                                       dptr(a0), dptr(m0), ctypes.byref(t0)))
             cols.append((g, dt, a, m, a0, m0))
-        lens = np.array([c[1].shape[0] for c in cols], np.int64)
-        W = int(lens.max()) if n_records is None else int(n_records)
-
-        def stack(i, shape):
-            out = np.zeros((W, len(cols)) + shape)
-            for k, c in enumerate(cols):
-                m = min(W, c[i].shape[0])
-                out[:m, k] = c[i][:m]
-            return out
-        win = cls.from_arrays(stack(0, (3,)), stack(1, ()), stack(2, (3,)), stack(3, (3,)),
-                              np.stack([c[4] for c in cols]), np.stack([c[5] for c in cols]))
-        win.counts = np.minimum(lens, W).astype(np.int32)
+        lens = [c[1].shape[0] for c in cols]
+        (g, counts), (dt, _), (a, _), (m, _) = (_stack_ragged([c[i] for c in cols], lens, n_records) for i in range(4))
+        win = cls.from_arrays(g, dt, a, m, np.stack([c[4] for c in cols]), np.stack([c[5] for c in cols]))
+        win.counts = counts
         return win
 
     def download_filters(self, cols):
         """The records of filter columns `cols` as float64 arrays: (gyro (W, n, 3), dt_ns (W, n), acc (W, n, 3),
         mag (W, n, 3), refs (n, 6))."""
-        cols = np.asarray(cols)
-        gd = self.gd.download((self.window, self.batch, 4), np.float64)[:, cols]
-        am = self.am.download((self.window, self.batch, 4), np.float64)[:, cols]
-        my = self.my.download((self.window, self.batch, 2), np.float64)[:, cols]
-        refs = self.refs.download((self.batch, 6), np.float64)[cols]
+        gd, am, my, refs = self._download(np.asarray(cols))
         return gd[..., :3], gd[..., 3], am[..., :3], np.concatenate([am[..., 3:4], my], axis=-1), refs
-
-    def wahba_quaternions(self, n_steps=None, step0=0, k_acc=0.5, k_mag=0.5):
-        """Pure-Wahba attitude of every record with fixed weights (main_file.py:40): (n_steps, batch, 4)."""
-        n_steps = self.window if n_steps is None else int(n_steps)
-        out = DeviceBuffer(32 * n_steps * self.batch)
-        check(lib.pekf_wahba_stream_rec64_dev(self.batch, n_steps, self.window, int(step0), self.am.ptr, self.my.ptr,
-                                              self.refs.ptr, float(k_acc), float(k_mag), out.ptr, None))
-        check(lib.pekf_device_sync())
-        return out.download((n_steps, self.batch, 4), np.float64)
-
-    def gyro_chain(self, q0=None, n_steps=None, step0=0, want_traj=False):
-        """Pure-gyro attitude (RK4 of the gyro records alone, KFS/KalmanFilter.cpp:149) from q0 (default
-        [1,0,0,0]); returns (q_final (batch,4), traj (n_steps,batch,4) or None)."""
-        n_steps = self.window if n_steps is None else int(n_steps)
-        q = np.tile([1.0, 0.0, 0.0, 0.0], (self.batch, 1)) if q0 is None else f64(q0, (self.batch, 4))
-        qb = DeviceBuffer(32 * self.batch).upload(q)
-        tb = DeviceBuffer(32 * n_steps * self.batch) if want_traj else None
-        check(lib.pekf_gyro_chain_rec64_dev(self.batch, n_steps, self.window, int(step0), self.gd.ptr, qb.ptr,
-                                            tb.ptr if tb is not None else None, None))
-        check(lib.pekf_device_sync())
-        return (qb.download((self.batch, 4), np.float64),
-                tb.download((n_steps, self.batch, 4), np.float64) if want_traj else None)
 
 
 # ------------------------------------------------------------------ server front-end (raw events)
@@ -413,28 +379,19 @@ def run_frontend(ev, alpha=0.1, r_max=None, events="f32"):
     tib = DeviceBuffer(8 * K).upload(np.ascontiguousarray(ev["t_init"], np.int64))
     cnt = DeviceBuffer(4 * K)
     errb = DeviceBuffer(4)
-    if events == "f64":
-        win = RecordWindow64(K, max(1, r_max))
-        errb.upload(np.zeros(1, np.int32))
-        check(lib.pekf_frontend_ext_dev(K, E, evb.ptr, init.ptr, tib.ptr, float(alpha), r_max, win.gd.ptr,
-                                        win.am.ptr, win.my.ptr, None, cnt.ptr, win.refs.ptr, flags, errb.ptr, None))
-        check(lib.pekf_device_sync())
-        if int(errb.download((1,), np.int32)[0]) & 2:
-            raise ValueError("more than r_max=%d records for some filter" % r_max)
-        win.counts = cnt.download((K,), np.int32)
-        return win, win.counts
-    win = IMUWindow(K, max(1, r_max))
+    win = (RecordWindow64 if events == "f64" else IMUWindow)(K, max(1, r_max))
     dtx = None
     while True:
         # without a side plane first; only if some record's dt does not fit the dt word (err bit 1: a
-        # pause of 2^31 ns or more) run again with one (8 B per record slot, kept in win.dtx)
+        # pause of 2^31 ns or more; never with FP64 events, whose records hold any dt) run again with one
+        # (8 B per record slot, kept in win.dtx)
         errb.upload(np.zeros(1, np.int32))
         check(lib.pekf_frontend_ext_dev(K, E, evb.ptr, init.ptr, tib.ptr, float(alpha), r_max, win.gd.ptr,
                                         win.am.ptr, win.my.ptr, dtx.ptr if dtx is not None else None, cnt.ptr,
                                         win.refs.ptr, flags, errb.ptr, None))
         check(lib.pekf_device_sync())
         err = int(errb.download((1,), np.int32)[0])
-        if err & 1 and dtx is None:
+        if err & 1 and dtx is None and events != "f64":
             dtx = DeviceBuffer(8 * K * max(1, r_max))
             continue
         break
@@ -456,16 +413,24 @@ def frontend_init(ev, n_avg=100, stats=True, events="f32"):
     K = np.asarray(ev["types"]).shape[1]
     evb, E, flags = _event_planes(ev, events)   # phase 2 always honours time events
     tsb = DeviceBuffer(8 * K).upload(np.ascontiguousarray(ev["t_init"], np.int64))
-    ib, tib, rb = DeviceBuffer(48 * K), DeviceBuffer(8 * K), DeviceBuffer(4 * K)
-    sb = DeviceBuffer(96 * K) if stats else None
-    check(lib.pekf_frontend_init_ext_dev(K, E, evb.ptr, tsb.ptr, int(n_avg), ib.ptr, tib.ptr,
-                                         sb.ptr if stats else None, rb.ptr, flags & EV_F64_EVENTS, None))
+    p2 = _launch_phase2(K, E, evb.ptr, tsb, n_avg, flags, stats=stats)
     check(lib.pekf_device_sync())
-    out = dict(init=ib.download((K, 6), np.float64), t_init=tib.download((K,), np.int64),
-               ready=rb.download((K,), np.int32).astype(bool))
+    out = dict(init=p2.init.download((K, 6), np.float64), t_init=p2.t_init.download((K,), np.int64),
+               ready=p2.ready.download((K,), np.int32).astype(bool))
     if stats:
-        st = sb.download((K, 12), np.float64)
+        st = p2.stats.download((K, 12), np.float64)
         out.update(gyro_mean=st[:, 0:3], var_acc=st[:, 3:6], var_mag=st[:, 6:9], var_gyro=st[:, 9:12])
+    return out
+
+
+def _launch_phase2(K, E, ev_ptr, t_start, n_avg, flags, stream=None, stats=False):
+    """pekf_frontend_init_ext_dev on the first E rows of device event planes (enqueued) -> its outputs as
+    DeviceBuffers: init (K, 6), t_init (K,) int64, ready (K,) int32 and, when asked for, stats (K, 12)."""
+    out = types.SimpleNamespace(init=DeviceBuffer(48 * K), t_init=DeviceBuffer(8 * K), ready=DeviceBuffer(4 * K),
+                                stats=DeviceBuffer(96 * K) if stats else None)
+    check(lib.pekf_frontend_init_ext_dev(K, int(E), ev_ptr, t_start.ptr, int(n_avg), out.init.ptr, out.t_init.ptr,
+                                         out.stats.ptr if stats else None, out.ready.ptr, flags & EV_F64_EVENTS,
+                                         stream))
     return out
 
 
@@ -552,6 +517,7 @@ class _Trajectory:
 
     def __init__(self, trajectory, n_events, batch, stream=None):
         self.rows, self.batch = trajectory_rows(trajectory, n_events), batch
+        self.wanted = trajectory is not None and trajectory is not False   # (a cap of 0 rows: the empty result)
         self.traj = self.dt = None
         if self.rows:
             self.traj, self.dt = DeviceBuffer(32 * self.rows * batch), DeviceBuffer(8 * self.rows * batch)
@@ -566,6 +532,35 @@ class _Trajectory:
         else:
             tr, dt = np.empty((0, K, 4)), np.empty((0, K))
         return dict(trajectory=tr, record_dt_ns=dt, record_times_ns=record_times_ns(t_init, dt))
+
+
+def _run_live(filters, ev_planes, n_events, init, t_init, alpha, flags, trajectory, stream=None):
+    """The fused launch every session ends in, run to completion: filters.run_events_async on device event
+    planes and phase-2 results, with the trajectory buffers `trajectory` asks for -> (counts, refs DeviceBuffers,
+    the _Trajectory)."""
+    K = filters.batch
+    cnt, refs = DeviceBuffer(4 * K), DeviceBuffer(48 * K)
+    tj = _Trajectory(trajectory, n_events, K, stream)
+    filters.run_events_async(ev_planes, n_events, init, t_init, cnt, refs, alpha, stream, flags=flags, traj=tj.traj,
+                             traj_dt=tj.dt, traj_rows=tj.rows)
+    check(lib.pekf_device_sync() if stream is None else lib.pekf_stream_sync(stream))
+    return cnt, refs, tj
+
+
+def _finish_session(filters, ev3, E3, p2, alpha, flags, trajectory, calibration, stream=None, from_frames=False):
+    """Phase 3 + the filter on phase 2's results (_launch_phase2's) and the dict run_session documents.
+    from_frames: calibration is _launch_calibration's, downloaded into the dict as calibration."""
+    K = filters.batch
+    cnt, refs, tj = _run_live(filters, ev3, E3, p2.init, p2.t_init, alpha, flags, trajectory, stream)
+    out = dict(ready=p2.ready.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
+               refs=refs.download((K, 6), np.float64))
+    if tj.wanted:
+        out.update(tj.result(p2.t_init.download((K,), np.int64)))
+    if from_frames:
+        calibration = out["calibration"] = _calibration_result(K, calibration)
+    if calibration is not None:
+        out["calibrated"] = np.asarray(calibration["calibrated"], bool).copy()
+    return out
 
 
 def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", events="f32", calibration=None,
@@ -593,24 +588,22 @@ def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", ev
     ev2, E2, flags2 = _event_planes(phase2, events)
     ev3, E3, flags3 = _event_planes(dict(phase3, t_init=t_last), events)
     tsb = DeviceBuffer(8 * K).upload(np.ascontiguousarray(phase2["t_init"], np.int64))
-    ib, tib, rb = DeviceBuffer(48 * K), DeviceBuffer(8 * K), DeviceBuffer(4 * K)
     if calibration is not None:
         _apply_calibration(calibration, K, E2, ev2.ptr, flags2)
         _apply_calibration(calibration, K, E3, ev3.ptr, flags3)
-    check(lib.pekf_frontend_init_ext_dev(K, E2, ev2.ptr, tsb.ptr, int(n_avg), ib.ptr, tib.ptr, None, rb.ptr,
-                                         flags2 & EV_F64_EVENTS, None))
-    cnt, refs = DeviceBuffer(4 * K), DeviceBuffer(48 * K)
-    tj = _Trajectory(trajectory, E3, K)
-    filters.run_events_async(ev3, E3, ib, tib, cnt, refs, alpha, flags=flags3 | _record_flags(records, events),
-                             traj=tj.traj, traj_dt=tj.dt, traj_rows=tj.rows)
-    check(lib.pekf_device_sync())
-    out = dict(ready=rb.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
-               refs=refs.download((K, 6), np.float64))
-    if trajectory is not None and trajectory is not False:
-        out.update(tj.result(tib.download((K,), np.int64)))
-    if calibration is not None:
-        out["calibrated"] = np.asarray(calibration["calibrated"], bool).copy()
-    return out
+    p2 = _launch_phase2(K, E2, ev2.ptr, tsb, n_avg, flags2)
+    return _finish_session(filters, ev3, E3, p2, alpha, flags3 | _record_flags(records, events), trajectory,
+                           calibration)
+
+
+def _frames_shape(frames):
+    """(n_frames, phones) of wire_events' frames, a host array or a (DeviceBuffer, n_frames, batch) triple."""
+    if isinstance(frames, tuple):
+        return int(frames[1]), int(frames[2])
+    shape = np.shape(frames)
+    if len(shape) != 3 or shape[2] != 100:
+        raise ValueError("frames must be [n_frames][batch][100] bytes")
+    return int(shape[0]), int(shape[1])
 
 
 def wire_events(frames, stream=None, frame_rows=False, phase1=False):
@@ -630,15 +623,12 @@ def wire_events(frames, stream=None, frame_rows=False, phase1=False):
     (batch,) int32; everything else is as without it, bit for bit.  Raises
     if a phone's frame is not in the client's form (wire.parse on the host reads any form std::stod
     does)."""
+    F, K = _frames_shape(frames)
     if isinstance(frames, tuple):
-        fb, F, K = frames
+        fb = frames[0]
     else:
         fr = np.ascontiguousarray(frames, np.uint8)
-        if fr.ndim != 3 or fr.shape[2] != 100:
-            raise ValueError("frames must be [n_frames][batch][100] bytes")
-        F, K = fr.shape[:2]
         fb = DeviceBuffer(max(fr.nbytes, 4)).upload(fr)
-    F, K = int(F), int(K)
     ev2, ev3 = DeviceBuffer(32 * max(F, 1) * K), DeviceBuffer(32 * max(F, 1) * K)
     t2b, n2b, n3b, badb = DeviceBuffer(8 * K), DeviceBuffer(4 * K), DeviceBuffer(4 * K), DeviceBuffer(4 * K)
     errb = DeviceBuffer(4).upload(np.zeros(1, np.int32))
@@ -695,41 +685,41 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     from_frames = isinstance(calibration, str)
     if from_frames and calibration != "frames":
         raise ValueError("calibration must be None, calibrate_magnetometer's dict or 'frames'")
-    if isinstance(frames, tuple):
-        Kf = int(frames[2])
-    else:
-        Kf = np.shape(frames)[1] if np.ndim(frames) == 3 else K  # (wire_events refuses any other shape)
+    Kf = _frames_shape(frames)[1]
     if Kf != K:  # the planes' column stride is the frames' phone count: any other batch reads them wrong
         raise ValueError("the frames are of %d phones, the filters of %d" % (Kf, K))
     w = wire_events(frames, stream, frame_rows, phase1=from_frames)
-    ib, tib, rb = DeviceBuffer(48 * K), DeviceBuffer(8 * K), DeviceBuffer(4 * K)
     if from_frames:
         calibration = _launch_calibration(K, w["E1"], w["ev1"].ptr, n_cal, EV_F64_EVENTS, stream)
     if calibration is not None:  # with frame rows the no-message rows are walked too (and left as they are)
         _apply_calibration(calibration, K, w["E2"], w["ev2"].ptr, EV_F64_EVENTS, stream)
         _apply_calibration(calibration, K, w["E3"], w["ev3"].ptr + 32 * K * w["ev3_from"], EV_F64_EVENTS, stream)
-    check(lib.pekf_frontend_init_ext_dev(K, w["E2"], w["ev2"].ptr, w["first_t2"].ptr, int(n_avg), ib.ptr, tib.ptr,
-                                         None, rb.ptr, EV_F64_EVENTS, stream))
-    cnt, refs = DeviceBuffer(4 * K), DeviceBuffer(48 * K)
+    p2 = _launch_phase2(K, w["E2"], w["ev2"].ptr, w["first_t2"], n_avg, EV_F64_EVENTS, stream)
     ev3 = w["ev3"]
     if w["ev3_from"]:  # (frame rows) the leading rows no phone has a phase-3 message in
         ev3 = types.SimpleNamespace(ptr=ev3.ptr + 32 * K * w["ev3_from"])
-    tj = _Trajectory(trajectory, w["E3"], K, stream)
-    filters.run_events_async(ev3, w["E3"], ib, tib, cnt, refs, alpha, stream, flags=EV_F64_EVENTS, traj=tj.traj,
-                             traj_dt=tj.dt, traj_rows=tj.rows)
-    check(lib.pekf_device_sync() if stream is None else lib.pekf_stream_sync(stream))
-    out = dict(ready=rb.download((K,), np.int32).astype(bool), counts=cnt.download((K,), np.int32),
-               refs=refs.download((K, 6), np.float64))
-    if trajectory is not None and trajectory is not False:
-        out.update(tj.result(tib.download((K,), np.int64)))
-    if from_frames:
-        calibration = out["calibration"] = _calibration_result(K, calibration)
-    if calibration is not None:
-        out["calibrated"] = np.asarray(calibration["calibrated"], bool).copy()
-    return out
+    return _finish_session(filters, ev3, w["E3"], p2, alpha, EV_F64_EVENTS, trajectory, calibration, stream,
+                           from_frames)
 
 
 # ------------------------------------------------------------------ the batched filter
+
+def _run_flags(precision, layout):
+    """the PEKF_RUN_* flags of a filter's precision and state layout"""
+    return (RUN_MIXED_PRECISION if precision == "mixed" else 0) | (RUN_STATE_SOA if layout == "soa" else 0)
+
+
+def _launch_counts(win, counts, n_steps, step0):
+    """A run's per-filter record counts as a DeviceBuffer of batch int32 (or None: every filter runs n_steps).
+    counts: an array of batch ints or a DeviceBuffer; default win.counts (ragged logs / front-end output) shifted
+    by step0, so each filter applies exactly its own records while sharing one launch."""
+    if counts is None and win.counts is not None:
+        counts = np.clip(np.asarray(win.counts, np.int64) - int(step0), 0, n_steps)
+    if counts is None or isinstance(counts, DeviceBuffer):
+        return counts
+    c = np.ascontiguousarray(counts, dtype=np.int32).reshape(win.batch)
+    return DeviceBuffer(c.nbytes).upload(c)
+
 
 class BatchedEKF:
     """B independent filters of the reference model, state resident on the device.
@@ -750,7 +740,7 @@ class BatchedEKF:
         self.batch = int(batch)
         self.q, self.r = float(q), float(r)
         self.layout = layout
-        self.flags = (RUN_MIXED_PRECISION if precision == "mixed" else 0) | (RUN_STATE_SOA if layout == "soa" else 0)
+        self.flags = _run_flags(precision, layout)
         self.X = DeviceBuffer(32 * self.batch)
         self.P = DeviceBuffer((80 if layout == "soa" else 128) * self.batch)
         self.reset()
@@ -813,17 +803,10 @@ class BatchedEKF:
     def run(self, win: IMUWindow, n_steps=None, step0=0, want_traj=False, counts=None):
         """Advance every filter n_steps records (default: the whole window) from row step0.
 
-        counts: per-filter record counts for this launch (array of batch ints or a DeviceBuffer);
-        default win.counts (ragged logs / front-end output) shifted by step0, so each filter
-        applies exactly its own records while sharing one launch."""
+        counts: per-filter record counts for this launch (_launch_counts: default win.counts from step0 on)."""
         n_steps = win.window if n_steps is None else int(n_steps)
         tb = DeviceBuffer(32 * n_steps * self.batch) if want_traj else None
-        if counts is None and win.counts is not None:
-            counts = np.clip(np.asarray(win.counts, np.int64) - int(step0), 0, n_steps)
-        if counts is not None and not isinstance(counts, DeviceBuffer):
-            c = np.ascontiguousarray(counts, dtype=np.int32).reshape(self.batch)
-            counts = DeviceBuffer(c.nbytes).upload(c)
-        self.run_async(win, n_steps, step0, None, tb, counts)
+        self.run_async(win, n_steps, step0, None, tb, _launch_counts(win, counts, n_steps, step0))
         check(lib.pekf_device_sync())
         if want_traj:
             return tb.download((n_steps, self.batch, 4), np.float64)
@@ -873,15 +856,9 @@ class BatchedEKF:
         init = DeviceBuffer(48 * self.batch).upload(
             np.concatenate([ev["init_acc"], ev["init_mag"]], axis=1).astype(np.float64))
         tib = DeviceBuffer(8 * self.batch).upload(np.ascontiguousarray(ev["t_init"], np.int64))
-        cnt, refs = DeviceBuffer(4 * self.batch), DeviceBuffer(48 * self.batch)
-        tj = _Trajectory(trajectory, E, self.batch)
-        self.run_events_async(evb, E, init, tib, cnt, refs, alpha, flags=flags | _record_flags(records, events),
-                              traj=tj.traj, traj_dt=tj.dt, traj_rows=tj.rows)
-        check(lib.pekf_device_sync())
+        cnt, refs, tj = _run_live(self, evb, E, init, tib, alpha, flags | _record_flags(records, events), trajectory)
         out = cnt.download((self.batch,), np.int32), refs.download((self.batch, 6), np.float64)
-        if trajectory is not None and trajectory is not False:
-            out += (tj.result(ev["t_init"]),)
-        return out
+        return out + (tj.result(ev["t_init"]),) if tj.wanted else out
 
 
 class FilterHandle:
@@ -898,11 +875,11 @@ class FilterHandle:
         mag0 = np.ascontiguousarray(mag0, np.float64).reshape(-1, 3)
         self.batch = acc0.shape[0]
         assert mag0.shape[0] == self.batch
-        flags = (RUN_MIXED_PRECISION if precision == "mixed" else 0) | (RUN_STATE_SOA if layout == "soa" else 0)
         t0 = None if t0_ns is None else np.ascontiguousarray(t0_ns, np.int64).reshape(self.batch)
         h = ctypes.c_void_p()
         check(lib.pekf_filter_create(self.batch, acc0.ctypes.data, mag0.ctypes.data, float(q), float(r),
-                                     t0.ctypes.data if t0 is not None else None, flags, ctypes.byref(h)))
+                                     t0.ctypes.data if t0 is not None else None, _run_flags(precision, layout),
+                                     ctypes.byref(h)))
         self.h = h.value
 
     def update(self, gyro, t_ns, acc, mag, missing=None, want_x=True):
@@ -922,12 +899,7 @@ class FilterHandle:
         n_steps = win.window if n_steps is None else int(n_steps)
         assert win.batch == self.batch
         tb = DeviceBuffer(32 * n_steps * self.batch) if want_traj else None
-        if counts is None and win.counts is not None:
-            counts = np.clip(np.asarray(win.counts, np.int64) - int(step0), 0, n_steps)
-        cb = None
-        if counts is not None:
-            c = np.ascontiguousarray(counts, dtype=np.int32).reshape(self.batch)
-            cb = DeviceBuffer(c.nbytes).upload(c)
+        cb = _launch_counts(win, counts, n_steps, step0)
         check(lib.pekf_filter_run_ext(self.h, n_steps, win.window, int(step0), win.gd.ptr, win.am.ptr, win.my.ptr,
                                       win.dtx.ptr if win.dtx is not None else None,
                                       tb.ptr if tb is not None else None, cb.ptr if cb is not None else None, None))

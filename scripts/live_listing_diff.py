@@ -1,19 +1,21 @@
 #!/usr/bin/env python3
-"""Are k_live's instantiations without trajectory output the kernels they were?
+"""Are the live path's kernels the kernels they were?
 
     hipcc <COMMON> <LIVEFLAGS> --cuda-device-only -S pekf_live.hip -o new.s      (this tree)
     the same on the previous commit's pekf_live.hip                 -o old.s
     live_listing_diff.py old.s new.s
 
-Each k_live<TE, R64, EV64[, TRAJ = false]> body -- instructions and block labels, comments and assembler
-directives dropped, the kernel's own name and its number in the .LBB labels normalised -- of old.s is compared
-with that of new.s.  Prints a line per kernel (lines, identical or the unified diff) and exits 1 on any
-difference.  Kernels with TRAJ = true are listed with their length only."""
+and the same for pekf_live_traj.hip (the TRAJ = true kernels) and pekf_frontend.hip (k_frontend, k_frontend_init;
+the Makefile's flags for that file: COMMON alone).  Each kernel template instantiation over bools of namespace
+pekf -- k_live<TE, R64, EV64, TRAJ>, k_frontend<TE, EV64>, k_frontend_init<EV64> -- of old.s is compared with
+that of new.s: instructions and block labels, comments and assembler directives dropped, the kernel's own name
+and its number in the .LBB labels normalised.  Prints a line per kernel (lines, identical or the unified diff)
+and exits 1 on any difference, or on a kernel that only one of the listings has."""
 import difflib
 import re
 import sys
 
-NAME = re.compile(r"^(_ZN4pekf6k_liveILb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?E\w*):\s*(;.*)?$")
+NAME = re.compile(r"^(_ZN4pekf\d+(k_[a-z_]+)I((?:Lb\dE)+)E\w*):\s*(;.*)?$")
 
 
 def kernels(path):
@@ -22,7 +24,7 @@ def kernels(path):
         m = NAME.match(line)
         if m:
             name, cur = m.group(1), []
-            out[tuple(int(v or 0) for v in m.group(2, 3, 4, 5))] = cur
+            out["%s<%s>" % (m.group(2), ", ".join(re.findall(r"Lb(\d)E", m.group(3))))] = cur
             continue
         if cur is None:
             continue
@@ -40,18 +42,13 @@ def kernels(path):
 def main(old_path, new_path):
     old, new = kernels(old_path), kernels(new_path)
     bad = 0
-    for key in sorted(new):
-        te, r64, ev64, traj = key
-        label = "k_live<TE=%d, R64=%d, EV64=%d, TRAJ=%d>" % key
-        if traj:
-            print("%s: %d lines (new)" % (label, len(new[key])))
-            continue
-        if key not in old:
-            print("%s: not in %s" % (label, old_path))
+    for label in sorted(set(old) | set(new)):
+        if label not in old or label not in new:
+            print("%s: not in %s" % (label, new_path if label in old else old_path))
             bad += 1
             continue
-        d = list(difflib.unified_diff(old[key], new[key], "old", "new", lineterm="", n=2))
-        print("%s: %d lines before, %d after, %s" % (label, len(old[key]), len(new[key]),
+        d = list(difflib.unified_diff(old[label], new[label], "old", "new", lineterm="", n=2))
+        print("%s: %d lines before, %d after, %s" % (label, len(old[label]), len(new[label]),
                                                      "identical" if not d else "DIFFERENT"))
         if d:
             bad += 1
