@@ -263,7 +263,7 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     // (TRAJ: q_W held for the rows, as k_run's TRAJ kernels hold it; converting late needs it only at the end)
     constexpr bool kLate = TRAJ && PEKF_LIVE_TRAJ_LATE;
     const auto Wr = enter_ref_basis<TRAJ && !kLate>(Wf, refs + 6 * b, false, x, P, rs);
-    const StepK<double> kc = step_consts<double, true>(qs, rs);
+    const StepK kc = step_consts<false, kLoopForm>(qs, rs);
 
     using Queue = std::conditional_t<EV64, RecordQueue<SlotsF64, kQueue>,
                                      std::conditional_t<R64, RecordQueue<SlotsLpf, kQueue>, RecordQueue<SlotsF32, kQueue>>>;
@@ -285,10 +285,9 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
             double gy[3], acc[3], mag[3];
             Queue::unpack(cur, gy, acc, mag);
             if (applied == 0)
-                ekf_record_step<double, true, false, true>(x, state_norm2(x), P, Wr, kc, gy, dt, false, acc, mag,
-                                                           reload);
-            else
-                ekf_record_step<double, true, true, true>(x, 1.0, P, Wr, kc, gy, dt, false, acc, mag, reload);
+                ekf_record_step<kLoopForm>(x, state_norm2(x), P, Wr, kc, gy, dt, false, acc, mag, reload);
+            else  // LAZY
+                ekf_record_step<kLoopForm, true>(x, 1.0, P, Wr, kc, gy, dt, false, acc, mag, reload);
             if constexpr (TRAJ) {
                 if (applied < traj_rows) {
                     const int64_t row = (int64_t)applied * batch + b;

@@ -165,16 +165,14 @@ PEKF_DEV void rotm_to_quat(const double *M, double *q) {
 }
 
 // ------------------------------- reciprocal / rsqrt ------------------------------------------
-// FAST = false: IEEE division and sqrt (per-call kernels).  FAST = true (fused kernel): the
+// The fused kernels' forms (the per-call kernels divide and take sqrt in IEEE arithmetic: rsqrt<0>): the
 // hardware v_rcp_f64 / v_rsq_f64 seed (measured on MI355X: <= 5.6e-8 relative) plus ONE Newton
 // step, measured <= 11 ulp (rcp) / <= 19 ulp (rsq), i.e. <= 4.2e-15 relative, over 1e-6..1e6
 // (scripts/probe_fp64.hip); a second step would give 0 / 2 ulp for 4 more FP64 ops each.
 // No scale / fixup sequences: operands here are positive and normal (DESIGN.md "FP64 budget").
 constexpr int kNewtonSteps = 1;
 
-template <bool FAST>
 PEKF_DEV double recip(double x) {
-    if (!FAST) return 1.0 / x;
     double r = __builtin_amdgcn_rcp(x);
 #pragma unroll
     for (int it = 0; it < kNewtonSteps; ++it) r = fma(r, fma(-x, r, 1.0), r);
@@ -512,8 +510,13 @@ PEKF_DEV void rotm_to_quat_fast(const double *M, double *q) {
     q[0] = v[0] * inv_s; q[1] = v[1] * inv_s; q[2] = v[2] * inv_s; q[3] = v[3] * inv_s;
 }
 
-// v = Q4(M) z with Q4 = 4 q q^T of the rotation M (see rotm_to_quat_toward); nv = |v|^2,
-// t0 = 1 + tr M = 4 qw^2
+// v = Q4 z with Q4 = 4 q q^T, q = RotationMatrix2Quart(M) of the rotation M (Wahba.py:19-47).  The four
+// candidate numerators of RotationMatrix2Quart are the columns of Q4 (diagonal 1 +- M00 +- M11 +- M22,
+// off-diagonal the sums / differences of M's off-diagonal pairs), so v = 4 q (q.z) is q already
+// carrying the sign of q.z: v / |v| is q flipped into z's hemisphere (ExtendedKalmanFilter.py:73-75),
+// with no branch selects and no separate hemisphere test.  nv = |v|^2 = (4 |q.z| |z|)^2 and
+// t0 = 1 + tr M = 4 qw^2 are what the callers' fallback tests read (wahba_quat_toward(const Frame &, ..),
+// wahba_matrix_toward).
 PEKF_DEV void q4_times(const double *M, const double *z, double *v, double &nv, double &t0) {
     const double a = 1.0 + M[8], b = 1.0 - M[8], s = M[0] + M[4], d = M[0] - M[4];
     t0 = a + s;
@@ -534,25 +537,6 @@ PEKF_DEV void rotm_to_quat_flip_reference(const double *M, const double *z, doub
     rotm_to_quat_scaled(M, v, inv_s);
     const double cmp = v[0] * z[0] + v[1] * z[1] + v[2] * z[2] + v[3] * z[3];
     sc = cmp < 0.0 ? -inv_s : inv_s;
-}
-
-// Y = RotationMatrix2Quart(M) flipped into z's hemisphere (Wahba.py:19-47, then
-// ExtendedKalmanFilter.py:73-75), for the fused kernel, returned as Y = v * sc.  The four candidate numerators of
-// RotationMatrix2Quart are the columns of Q4 = 4 q q^T (diagonal 1 +- M00 +- M11 +- M22,
-// off-diagonal the sums / differences of M's off-diagonal pairs), so v = Q4 z = 4 q (q.z) is q
-// already carrying the sign of q.z: Y = v / |v|, no branch selects and no separate hemisphere
-// test.  |v| = 4 |q.z| |z|, so where q is nearly orthogonal to z (|q.z| < 1/4: the measured
-// attitude more than 150 degrees from the prediction) and where the reference's own branch
-// formula is ill-conditioned (a rotation within ~1e-5 rad of the identity, where it divides by
-// ~0 and, at the exact identity, returns NaN) the lane takes the reference's branch formula and
-// strict '<' flip instead.  Neither occurs on a tracked stream, so the fallback costs a wave
-// nothing unless one of its lanes needs it.
-PEKF_DEV void rotm_to_quat_toward(const double *M, const double *z, double *v, double &sc) {
-    double nv, t0;
-    q4_times(M, z, v, nv, t0);
-    sc = rsqrt<true>(nv);  // (the common path carries no data merge with the rare branch)
-    if (PEKF_TAKEN(nv < 1.0 || t0 > 4.0 - 1e-10, false))
-        rotm_to_quat_flip_reference(M, z, v, sc);  // (NaN operands never get here)
 }
 
 // ------------------------------- reference-frame basis ---------------------------------------
@@ -631,8 +615,8 @@ PEKF_DEV void quat_to_rotm(const double *q, double *M) {
 struct NoPin {
     PEKF_DEV void operator()() const {}
 };
-// The matrix chain: the current frame Fv, R' = Rz(theta) Fv^T, Q4 = I + K(R') and v = Q4 z (as
-// rotm_to_quat_toward).  It is the fallback body of wahba_toward_from_product below (behind PEKF_TAKEN
+// The matrix chain: the current frame Fv, R' = Rz(theta) Fv^T, Q4 = I + K(R') and v = Q4 z
+// (q4_times).  It is the fallback body of wahba_toward_from_product below (behind PEKF_TAKEN
 // there), for the lanes the product form does not serve: a measurement more than ~150 degrees from the
 // prediction, a negative magnetometer weight and a NaN (degenerate) frame.  reload(acc, mag): the
 // record's samples again; the caller re-reads them (memory, LDS).
@@ -780,7 +764,14 @@ PEKF_DEV void wahba_quat_toward(const RW &W, const double *acc, const double *ma
     wahba_toward_from_product<F>(W, q, km, z, v, sc, reload, pin);
 }
 
-// Y = v * sc in the world basis (the per-record kernels)
+// Y = v * sc in the world basis (the plain form of ekf_record_step) from the two frames: the matrix chain
+// R = Fw diag(P2, 1) Fv^T (wahba_rotation), v = Q4 z (q4_times) and sc = 1 / |v|.  |v| = 4 |q.z| |z|, so
+// where q is nearly orthogonal to z (|q.z| < 1/4: the measured attitude more than 150 degrees from the
+// prediction) and where the reference's own branch formula is ill-conditioned (a rotation within
+// ~1e-5 rad of the identity, where it divides by ~0 and, at the exact identity, returns NaN) the lane
+// takes the reference's branch formula and strict '<' flip instead (rotm_to_quat_flip_reference).
+// Neither occurs on a tracked stream, so the fallback costs a wave nothing unless one of its lanes
+// needs it, and the common path carries no data merge with the rare branch.
 template <int F = 1, class Reload, class Pin = NoPin>
 PEKF_DEV void wahba_quat_toward(const Frame &W, const Frame &V, double ka, double km, const double *z, double *v,
                                 double &sc, const Reload &reload, const Pin & = Pin()) {
@@ -788,7 +779,7 @@ PEKF_DEV void wahba_quat_toward(const Frame &W, const Frame &V, double ka, doubl
     wahba_rotation<true>(W, V, ka, km, R);
     q4_times(R, z, v, nv, t0);
     sc = rsqrt<true>(nv);
-    // rotm_to_quat_toward's fallback, taken for NaN too (a degenerate current frame: rank-1 B)
+    // (taken for NaN too: a degenerate current frame, rank-1 B)
     if (PEKF_TAKEN(!(nv >= 1.0) || t0 > 4.0 - 1e-10, false)) {
         rotm_to_quat_flip_reference(R, z, v, sc);
         // NaN: a degenerate current frame, solved from the re-read samples (see the reference-basis form)
@@ -801,6 +792,17 @@ PEKF_DEV void wahba_quat_toward(const Frame &W, const Frame &V, double ka, doubl
             sc = v[0] * z[0] + v[1] * z[1] + v[2] * z[2] + v[3] * z[3] < 0.0 ? -1.0 : 1.0;
         }
     }
+}
+
+// The same from the record's samples, the reference-basis form's arguments: one call for either basis.
+// The callers' ka = |acc_z| >= 0, so wahba_sign(ka, km) is the sign of km = 1 - ka (never -0), which is
+// all make_frame reads of its sg.
+template <int F = 1, class Reload, class Pin = NoPin>
+PEKF_DEV void wahba_quat_toward(const Frame &W, const double *acc, const double *mag, double ka, double km,
+                                const double *z, double *v, double &sc, const Reload &reload, const Pin &pin = Pin()) {
+    Frame V;
+    make_frame<F>(acc, mag, V, km);
+    wahba_quat_toward<F>(W, V, ka, km, z, v, sc, reload, pin);
 }
 
 // ------------------------------- fused-step forms --------------------------------------------
@@ -838,9 +840,7 @@ PEKF_DEV Sym4T<T> sym_rotate(const double *q, const Sym4T<T> &S) {
 
 // single-precision reciprocal for the opt-in mixed-precision covariance path: v_rcp_f32
 // (1 ulp) + one Newton step
-template <bool FAST>
 PEKF_DEV float recip(float x) {
-    if (!FAST) return 1.0f / x;
     float r = __builtin_amdgcn_rcpf(x);
     return fmaf(r, fmaf(-x, r, 1.0f), r);
 }
@@ -861,27 +861,26 @@ PEKF_DEV float recip(float x) {
 //   L(u) R(h) = [[-u.h, (u x h)^T], [u x h, (u.h) I - u h^T - h u^T]].
 // u needs only the trace butterflies of P's diagonal and the sums / differences of its off-diagonal
 // pairs: 71 FP64 operations for 2S against 96 for the direct Omega P Omega^T + Jb Q Jb^T + rI.
-template <typename T>
-PEKF_DEV Sym4T<T> innovation_cov2(const Sym4T<T> &P, const T *h, const T *w, T th2, const T *x, T n2, T g2, T r2,
-                                  T g2x) {
+PEKF_DEV Sym4 innovation_cov2(const Sym4 &P, const double *h, const double *w, double th2, const double *x, double n2,
+                              double g2, double r2, double g2x) {
     // U = 4u, U_a = D_aa h_a + sum_{b != a} D_ab h_b with D_ab = tr(L(e_a) R(e_b) P):
     //   D_11 = -P00 - P11 + P22 + P33, D_22 = -P00 + P11 - P22 + P33, D_33 = -P00 + P11 + P22 - P33,
     //   D_12 = 2(P03 - P12), D_21 = -2(P03 + P12), D_13 = -2(P02 + P13), D_31 = 2(P02 - P13),
     //   D_23 = 2(P01 - P23), D_32 = -2(P01 + P23)
-    const T sp = P.a00 + P.a11, dp = P.a11 - P.a00, sq = P.a22 + P.a33, dq = P.a22 - P.a33;
-    const T tr = sp + sq, d11 = sq - sp, d22 = dp - dq, d33 = dp + dq;
-    const T u0 = fma(d11, h[0], fma(P.a03 - P.a12, w[1], -(P.a02 + P.a13) * w[2]));
-    const T u1 = fma(d22, h[1], fma(P.a01 - P.a23, w[2], -(P.a03 + P.a12) * w[0]));
-    const T u2 = fma(d33, h[2], fma(P.a02 - P.a13, w[0], -(P.a01 + P.a23) * w[1]));
-    const T uh = fma(u0, h[0], fma(u1, h[1], u2 * h[2]));                   // 4u . h
-    const T c0 = fma(u1, h[2], -u2 * h[1]), c1 = fma(u2, h[0], -u0 * h[2]);  // 4u x h
-    const T c2 = fma(u0, h[1], -u1 * h[0]);
-    const T nt = T(-2) * th2;
+    const double sp = P.a00 + P.a11, dp = P.a11 - P.a00, sq = P.a22 + P.a33, dq = P.a22 - P.a33;
+    const double tr = sp + sq, d11 = sq - sp, d22 = dp - dq, d33 = dp + dq;
+    const double u0 = fma(d11, h[0], fma(P.a03 - P.a12, w[1], -(P.a02 + P.a13) * w[2]));
+    const double u1 = fma(d22, h[1], fma(P.a01 - P.a23, w[2], -(P.a03 + P.a12) * w[0]));
+    const double u2 = fma(d33, h[2], fma(P.a02 - P.a13, w[0], -(P.a01 + P.a23) * w[1]));
+    const double uh = fma(u0, h[0], fma(u1, h[1], u2 * h[2]));                   // 4u . h
+    const double c0 = fma(u1, h[2], -u2 * h[1]), c1 = fma(u2, h[0], -u0 * h[2]);  // 4u x h
+    const double c2 = fma(u0, h[1], -u1 * h[0]);
+    const double nt = -2.0 * th2;
     // diagonal constant: 2 (2|h|^2 tr(P)/4 + g |x|^2 + r), -/+ 4u.h
-    const T base = fma(th2, tr, fma(g2, n2, r2));
-    const T b0 = base - uh, bk = base + uh;
-    const T gx0 = g2x * x[0], gx1 = g2x * x[1], gx2 = g2x * x[2], gx3 = g2x * x[3];
-    Sym4T<T> o;
+    const double base = fma(th2, tr, fma(g2, n2, r2));
+    const double b0 = base - uh, bk = base + uh;
+    const double gx0 = g2x * x[0], gx1 = g2x * x[1], gx2 = g2x * x[2], gx3 = g2x * x[3];
+    Sym4 o;
     o.a00 = fma(nt, P.a00, fma(-gx0, x[0], b0));
     o.a01 = fma(nt, P.a01, fma(-gx0, x[1], c0));
     o.a02 = fma(nt, P.a02, fma(-gx0, x[2], c1));
@@ -896,7 +895,7 @@ PEKF_DEV Sym4T<T> innovation_cov2(const Sym4T<T> &P, const T *h, const T *w, T t
 }
 
 // The same for the covariance carried as N, P = rI + beta D N D with beta = sqrt(2) r and
-// D = diag(1, 1, -1, -1) (the multi-record stream loop): returns S^ = 2S / beta, for which
+// D = diag(1, 1, -1, -1) (the loop form of ekf_record_step): returns S^ = 2S / beta, for which
 // spd_inverse_schur<NEG = true> gives the next record's N = -D (S^)^-1 D with no scaling at all
 // (P+ = rI - r^2 S^-1 = rI - (2r^2/beta) (S^)^-1 = rI - beta (S^)^-1, since 2r^2 = beta^2), so the
 // update P = rI - r^2 S^-1 costs nothing.  D flips the sign of the off-diagonal 2x2 block: in that
@@ -906,42 +905,13 @@ PEKF_DEV Sym4T<T> innovation_cov2(const Sym4T<T> &P, const T *h, const T *w, T t
 //   S^ = 2 A N' A^T + (2/beta)(r|h|^2 + r) I + (2g/beta)(|x|^2 I - x x^T),
 // innovation_cov2's algebra on N' with gb = 2g/beta, rb = 2r/beta (= sqrt 2) for 2g, 2r, and one
 // operation more (tr N + rb); gbx = gb / |x|^2 as innovation_cov2's g2x.
-template <typename T>
-PEKF_DEV Sym4T<T> innovation_cov_n(const Sym4T<T> &N, const T *h, const T *w, T th2, const T *x, T n2, T gb, T rb,
-                                   T gbx) {
-    const T sp = N.a00 + N.a11, dp = N.a11 - N.a00, sq = N.a22 + N.a33, dq = N.a22 - N.a33;
-    const T tr = sp + sq, d11 = sq - sp, d22 = dp - dq, d33 = dp + dq;
-    const T u0 = fma(d11, h[0], fma(N.a12 - N.a03, w[1], (N.a02 + N.a13) * w[2]));
-    const T u1 = fma(d22, h[1], fma(N.a01 - N.a23, w[2], (N.a03 + N.a12) * w[0]));
-    const T u2 = fma(d33, h[2], fma(N.a13 - N.a02, w[0], -(N.a01 + N.a23) * w[1]));
-    const T uh = fma(u0, h[0], fma(u1, h[1], u2 * h[2]));
-    const T c0 = fma(u1, h[2], -u2 * h[1]), c1 = fma(u2, h[0], -u0 * h[2]);
-    const T c2 = fma(u0, h[1], -u1 * h[0]);
-    const T nt = T(-2) * th2;
-    const T base = fma(th2, tr + rb, fma(gb, n2, rb));
-    const T b0 = base - uh, bk = base + uh;
-    const T gx0 = gbx * x[0], gx1 = gbx * x[1], gx2 = gbx * x[2], gx3 = gbx * x[3];
-    Sym4T<T> o;
-    o.a00 = fma(nt, N.a00, fma(-gx0, x[0], b0));
-    o.a01 = fma(nt, N.a01, fma(-gx0, x[1], c0));
-    o.a02 = fma(-nt, N.a02, fma(-gx0, x[2], c1));
-    o.a03 = fma(-nt, N.a03, fma(-gx0, x[3], c2));
-    o.a11 = fma(nt, N.a11, fma(-gx1, x[1], fma(-u0, w[0], bk)));
-    o.a22 = fma(nt, N.a22, fma(-gx2, x[2], fma(-u1, w[1], bk)));
-    o.a33 = fma(nt, N.a33, fma(-gx3, x[3], fma(-u2, w[2], bk)));
-    o.a12 = fma(-nt, N.a12, fma(-gx1, x[2], -fma(u0, h[1], u1 * h[0])));
-    o.a13 = fma(-nt, N.a13, fma(-gx1, x[3], -fma(u0, h[2], u2 * h[0])));
-    o.a23 = fma(nt, N.a23, fma(-gx2, x[3], -fma(u1, h[2], u2 * h[1])));
-    return o;
-}
-
-// innovation_cov_n in FP64 from the raw gyro sample w alone, for the omod build of the multi-record
-// loop (OmodMode): every product with h = w/2 becomes the product with w halved by the instruction
-// that forms it (omod div:2), and th2x2 = 2|h|^2 = |w|^2/2 replaces both |h|^2 and -2|h|^2 (the
-// latter as a negated operand), so the gyro needs no scaling at all.  Every value equals
-// innovation_cov_n's bit for bit: d_aa h_a = (d_aa/2) w_a, u.h = (u.w)/2 and u x h = (u x w)/2 with
-// each rounding of a halved exact sum, |h|^2 (tr + rb) = th2x2 ((tr + rb)/2).  rbh = rb / 2.
-PEKF_DEV Sym4 innovation_cov_n_w(const Sym4 &N, const double *w, double th2x2, const double *x, double n2, double gb,
+// It is written from the raw gyro sample w alone and runs only inside an OmodMode: every product with
+// h = w/2 is the product with w halved by the instruction that forms it (omod div:2), and
+// th2x2 = 2|h|^2 = |w|^2/2 replaces both |h|^2 and -2|h|^2 (the latter as a negated operand), so the
+// gyro needs no scaling at all.  Every value equals, bit for bit, that of the same algebra written with
+// h and multiplies by 1/2: d_aa h_a = (d_aa/2) w_a, u.h = (u.w)/2 and u x h = (u x w)/2 with each
+// rounding of a halved exact sum, |h|^2 (tr + rb) = th2x2 ((tr + rb)/2).  rbh = rb / 2.
+PEKF_DEV Sym4 innovation_cov_n(const Sym4 &N, const double *w, double th2x2, const double *x, double n2, double gb,
                                  double rb, double rbh, double gbx) {
     const double sp = N.a00 + N.a11, dp = N.a11 - N.a00, sq = N.a22 + N.a33, dq = N.a22 - N.a33;
     const double trh = add_half(sp, sq) + rbh;  // (tr + rb) / 2
@@ -977,9 +947,9 @@ PEKF_DEV Sym4 innovation_cov_n_w(const Sym4 &N, const double *w, double th2x2, c
 // NEG = true returns -D S^-1 D, D = diag(1, 1, -1, -1), for the same work: with W = X (-C^-1) it is
 // [[-A^-1 + W X^T, W], [W^T, -C^-1]], every entry a plain sum of products (the sign of -C^-1 rides on
 // the second reciprocal, that of -A^-1 on an addend).
-template <typename T, bool FAST = true, bool NEG = false>
+template <bool NEG = false, typename T>
 PEKF_DEV Sym4T<T> spd_inverse_schur(const Sym4T<T> &S) {
-    const T ia = recip<FAST>(S.a00 * S.a11 - S.a01 * S.a01);
+    const T ia = recip(S.a00 * S.a11 - S.a01 * S.a01);
     const T p00 = S.a11 * ia, p01 = -S.a01 * ia, p11 = S.a00 * ia;  // A^-1
     // X = A^-1 B, B = [[a02, a03], [a12, a13]]
     const T x00 = p00 * S.a02 + p01 * S.a12, x01 = p00 * S.a03 + p01 * S.a13;
@@ -988,7 +958,7 @@ PEKF_DEV Sym4T<T> spd_inverse_schur(const Sym4T<T> &S) {
     const T c00 = S.a22 - S.a02 * x00 - S.a12 * x10;
     const T c01 = S.a23 - S.a02 * x01 - S.a12 * x11;
     const T c11 = S.a33 - S.a03 * x01 - S.a13 * x11;
-    const T ic = NEG ? recip<FAST>(c01 * c01 - c00 * c11) : recip<FAST>(c00 * c11 - c01 * c01);
+    const T ic = NEG ? recip(c01 * c01 - c00 * c11) : recip(c00 * c11 - c01 * c01);
     const T q00 = c11 * ic, q01 = -c01 * ic, q11 = c00 * ic;        // C^-1 (NEG: -C^-1)
     Sym4T<T> o;
     if (NEG) {
@@ -1018,7 +988,7 @@ PEKF_DEV Sym4T<T> spd_inverse_schur(const Sym4T<T> &S) {
 }
 
 // Upper triangle of s A B for symmetric A and B that commute (so A B is symmetric): the
-// mixed-precision posterior P = r P- S^-1 (ekf_record_step_mixed).  50 operations.
+// mixed-precision posterior P = r P- S^-1 (the f32 ekf_record_step).  50 operations.
 template <typename T>
 PEKF_DEV Sym4T<T> sym_product_upper(const Sym4T<T> &A, const Sym4T<T> &B, T s) {
     const T a[4][4] = {{A.a00, A.a01, A.a02, A.a03}, {A.a01, A.a11, A.a12, A.a13},
@@ -1071,13 +1041,10 @@ PEKF_DEV void rk4_closed_w(const double *x, double n2, double dt_ns, const doubl
     z[3] = a * x[3] + w2 * x[0] + w1 * x[1] - w0 * x[2];
 }
 
+// rk4_closed for callers that want z alone
 PEKF_DEV void rk4_closed(const double *x, double n2, double dt_ns, const double *hw, double th2, double *z) {
     double kk, in;
     rk4_closed(x, n2, dt_ns, hw, th2, z, kk, in);
-}
-
-PEKF_DEV void rk4_closed(const double *x, double n2, double dt_ns, const double *hw, double *z) {
-    rk4_closed(x, n2, dt_ns, hw, hw[0] * hw[0] + hw[1] * hw[1] + hw[2] * hw[2], z);
 }
 
 }  // namespace pekf

@@ -437,7 +437,7 @@ struct Phase3T {
         // Parser::LinearInterpolationSensor (:259-267): (y2 - y1) / (t2 - t1) * (t3 - t1) + y1, the
         // division taken as one reciprocal.  Timestamps are integer ns held in doubles (exact below
         // 2^53), so t3 - t1 and t2 - t1 are the exact differences (double)t3 - (double)t1 gives.
-        const double fa = q.an * recip<true>(q.ad), fm = q.mn * recip<true>(q.md);
+        const double fa = q.an * recip(q.ad), fm = q.mn * recip(q.md);
         V3 a0 = widen(q.acc0), m0 = widen(q.mag0);
         const V3 a1 = widen(q.acc1), m1 = widen(q.mag1);
         // acc_0 / mag_0 can still be the phase-2 mean only up to a lane's first record, so the wave

@@ -21,21 +21,17 @@ __global__ __launch_bounds__(kRunBlock) void k_state_layout(int64_t batch, doubl
     const WaveTile tl(pool, tile_doubles<16>(), batch);
     const bool act = tl.active();
     const int64_t b = tl.first + tl.lane;
-    double x[4], pv[16];
+    StateMover<false, double> aos(tl, Xa, Pa, batch);
+    double x[4];
+    Sym4 S = {};
     if (to_soa) {  // uniform
-        double cx[4], cp[16];
-        tl.gather(Xa, cx);
-        tl.gather(Pa, cp);
-        tl.to_lanes(cx, x);
-        tl.to_lanes(cp, pv);
-        if (act) store_state<true>(Xs, Ps, b, batch, x, sym_from16<double>(pv));
+        aos.gather();
+        aos.to_lanes(b, x, S);
+        if (act) store_state<true>(Xs, Ps, b, batch, x, S);
     } else {
-        Sym4T<double> S = {};
         x[0] = x[1] = x[2] = x[3] = 0.0;
         if (act) load_state<true>(Xs, Ps, b, batch, x, S);
-        sym_to16(S, pv);
-        tl.store(Xa, x);
-        tl.store(Pa, pv);
+        aos.store(b, x, S);
     }
 }
 
@@ -51,10 +47,10 @@ __global__ __launch_bounds__(kRunBlock) void k_reset(int64_t batch, double *X, d
 }
 
 // One record per filter from the stream planes (pekf_run_dev with n_steps = 1: online serving), in
-// the world basis with the covariance as P.  The state and the reference pair are most of the
-// traffic: the AoS state and the [batch][6] reference pairs move in coalesced wave tiles
-// (pekf_tile.hpp) instead of 128 / 48 B-strided per-lane accesses; the SoA state is read and written
-// per lane, one contiguous 512 B access per component and wave.  No prefetch of a next record: its
+// the world basis with the covariance as P (ekf_record_step's plain form).  The state and the reference
+// pair are most of the traffic: the AoS state (StateMover) and the [batch][6] reference pairs move in
+// coalesced wave tiles (pekf_tile.hpp) instead of 128 / 48 B-strided per-lane accesses; the SoA state is read
+// and written per lane, one contiguous 512 B access per component and wave.  No prefetch of a next record: its
 // 40 B would be an eighth of the traffic.  The template flags are k_run's (pekf_step.hpp).
 template <bool TRAJ, bool MIXED, bool SOA, bool COUNTS, bool LONGDT>
 __global__ __launch_bounds__(kRunBlock) void k_run_one(int64_t batch, int64_t window, int64_t step0,
@@ -68,26 +64,18 @@ __global__ __launch_bounds__(kRunBlock) void k_run_one(int64_t batch, int64_t wi
     constexpr int kTile = SOA ? 6 : 16;
     __shared__ double pool[kRunBlock / kWave * tile_doubles<kTile>()];
     const WaveTile t(pool, tile_doubles<kTile>(), batch);
-    double cx[4], cp[16], cr[6];
-    if constexpr (!SOA) {
-        t.gather(Xio, cx);
-        t.gather(Pio, cp);
-    }
+    StateMover<SOA, PT> state(t, Xio, Pio, batch);
+    double cr[6];
+    state.gather();
     t.gather(refs, cr);
     const bool act = t.active();
     const uint32_t lane = act ? (uint32_t)(t.first + t.lane) : 0u;  // idle lanes read a valid row
     const int64_t base = (step0 % window) * batch;
     const Rec cur = {(gd + base)[lane], (am + base)[lane], (my + base)[lane]};
     const bool run = act && (!COUNTS || counts[lane] > 0);
-    double x[4], pv[16], rf[6];
+    double x[4], rf[6];
     Sym4T<PT> P;
-    if constexpr (SOA) {
-        load_state<true>(Xio, Pio, lane, batch, x, P);
-    } else {
-        t.to_lanes(cx, x);
-        t.to_lanes(cp, pv);
-        P = sym_from16<PT>(pv);
-    }
+    state.to_lanes(lane, x, P);
     t.to_lanes(cr, rf);
     Frame Wf;
     make_frame<true>(rf, rf + 3, Wf);
@@ -106,30 +94,20 @@ __global__ __launch_bounds__(kRunBlock) void k_run_one(int64_t batch, int64_t wi
             a[0] = va.x; a[1] = va.y; a[2] = va.z;
             m[0] = va.w; m[1] = vm.x; m[2] = vm.y;
         };
-        if constexpr (MIXED)
-            ekf_record_step_mixed<false, true>(x, state_norm2(x), P, Wf, step_consts_mixed(qs, rs), gy, dtn,
-                                               (word & PEKF_MISSING_MAG_BIT) != 0, acc, mag, reload);
-        else
-            ekf_record_step<PT>(x, state_norm2(x), P, Wf, step_consts<PT, false>(qs, rs), gy, dtn,
-                                (word & PEKF_MISSING_MAG_BIT) != 0, acc, mag, reload);
+        ekf_record_step<kPlainForm>(x, state_norm2(x), P, Wf, step_consts<MIXED, kPlainForm>(qs, rs), gy, dtn,
+                                    (word & PEKF_MISSING_MAG_BIT) != 0, acc, mag, reload);
     }
     if (TRAJ && act) {
         double2 *o = reinterpret_cast<double2 *>(traj) + 2 * (int64_t)lane;
         o[0] = make_double2(x[0], x[1]);
         o[1] = make_double2(x[2], x[3]);
     }
-    if constexpr (SOA) {
-        if (act) store_state<true>(Xio, Pio, lane, batch, x, P);
-    } else {
-        sym_to16(P, pv);
-        t.store(Xio, x);
-        t.store(Pio, pv);
-    }
+    state.store(lane, x, P);
 }
 
 // One record per filter from FP64 arrays (the filter handle's online update,
 // pekf_filter_update): dt = t - previousT per filter (ExtendedKalmanFilter.py:62,67), then the
-// same ekf_record_step as the stream kernel.  Record arrays are filter-major ([batch][3]).
+// same plain-form ekf_record_step as k_run_one.  Record arrays are filter-major ([batch][3]).
 template <bool MIXED, bool SOA>
 __global__ __launch_bounds__(kRunBlock) void k_update(int64_t batch, const double *__restrict__ gyro,
                                                       const int64_t *__restrict__ t_ns,
@@ -146,6 +124,7 @@ __global__ __launch_bounds__(kRunBlock) void k_update(int64_t batch, const doubl
     const WaveTile tl(pool, tile_doubles<kW>(), batch);
     const bool act = tl.active();
     const int64_t b = act ? tl.first + tl.lane : 0;  // idle lanes compute on filter 0, store nothing
+    StateMover<SOA, PT> state(tl, Xio, Pio, batch);
     double cr[6], cg[3], ca[3], cm[3];
     tl.gather(refs, cr);
     tl.gather(gyro, cg);
@@ -153,17 +132,8 @@ __global__ __launch_bounds__(kRunBlock) void k_update(int64_t batch, const doubl
     tl.gather(mag, cm);
     double x[4];
     Sym4T<PT> P;
-    double pv[16];
-    if constexpr (SOA) {
-        load_state<true>(Xio, Pio, b, batch, x, P);
-    } else {
-        double cx[4], cp[16];
-        tl.gather(Xio, cx);
-        tl.gather(Pio, cp);
-        tl.to_lanes(cx, x);
-        tl.to_lanes(cp, pv);
-        P = sym_from16<PT>(pv);
-    }
+    state.gather();
+    state.to_lanes(b, x, P);
     const int64_t t = t_ns[b];
     const double dt_ns = (double)(t - prev_t[b]);
     const bool miss = missing && missing[b];
@@ -181,19 +151,10 @@ __global__ __launch_bounds__(kRunBlock) void k_update(int64_t batch, const doubl
             rm[i] = mag[3 * b + i];
         }
     };
-    if constexpr (MIXED)
-        ekf_record_step_mixed<false, true>(x, state_norm2(x), P, Wf, step_consts_mixed(qs, rs), g, dt_ns, miss, a, m,
-                                           reload);
-    else
-        ekf_record_step<PT>(x, state_norm2(x), P, Wf, step_consts<PT, false>(qs, rs), g, dt_ns, miss, a, m, reload);
+    ekf_record_step<kPlainForm>(x, state_norm2(x), P, Wf, step_consts<MIXED, kPlainForm>(qs, rs), g, dt_ns, miss, a, m,
+                                reload);
     if (act) prev_t[b] = t;
-    if constexpr (SOA) {
-        if (act) store_state<true>(Xio, Pio, b, batch, x, P);
-    } else {
-        sym_to16(P, pv);
-        tl.store(Xio, x);
-        tl.store(Pio, pv);
-    }
+    state.store(b, x, P);
     if (x_out) tl.store(x_out, x);
 }
 

@@ -1,9 +1,10 @@
 // pekf_step.hpp -- device code of the fused hot path shared by pekf_run.hip (one-record launches,
 // the filter handle's update), pekf_run_multi.hip (multi-record launches over 40 B and FP64 records)
-// and pekf_live.hip: the state layouts, the record planes' row cursor, one record of main_file.py:42-45
-// on a lane's registers (ekf_record_step), the change to the reference frame's basis and the
-// multi-record stream kernel template k_run.  The files are compiled with different scheduling
-// strategies (Makefile), never different arithmetic.
+// and pekf_live.hip: the state layouts and the one-record kernels' state mover, the record planes' row
+// cursor, one record of main_file.py:42-45 on a lane's registers (ekf_record_step: the FP64 step in its
+// two forms, plain and loop, and the mixed-precision step, chosen by the covariance's type), the change
+// to the reference frame's basis and the multi-record stream kernel template k_run.  The files are
+// compiled with different scheduling strategies (Makefile), never different arithmetic.
 #pragma once
 
 #include <type_traits>
@@ -64,6 +65,62 @@ __device__ __forceinline__ void store_state(double *X, double *P, int64_t b, int
         po[12] = S.a03; po[13] = S.a13; po[14] = S.a23; po[15] = S.a33;
     }
 }
+
+// AoS P (full 4x4) <-> its upper triangle, for state moved through a WaveTile
+template <typename PT>
+__device__ __forceinline__ Sym4T<PT> sym_from16(const double (&p)[16]) {
+    return {(PT)p[0], (PT)p[1], (PT)p[2], (PT)p[3], (PT)p[5], (PT)p[6], (PT)p[7], (PT)p[10], (PT)p[11], (PT)p[15]};
+}
+template <typename PT>
+__device__ __forceinline__ void sym_to16(const Sym4T<PT> &S, double (&p)[16]) {
+    p[0] = S.a00; p[1] = S.a01; p[2] = S.a02; p[3] = S.a03;
+    p[4] = S.a01; p[5] = S.a11; p[6] = S.a12; p[7] = S.a13;
+    p[8] = S.a02; p[9] = S.a12; p[10] = S.a22; p[11] = S.a23;
+    p[12] = S.a03; p[13] = S.a13; p[14] = S.a23; p[15] = S.a33;
+}
+
+// The state of a one-record kernel (k_run_one, k_update; the AoS side of k_state_layout) between HBM
+// and the lanes.  AoS: X and P move through the wave's tile in coalesced blocks (pekf_tile.hpp) --
+// gather() starts the loads, where the kernel gathers its other operands; to_lanes() transposes them
+// where the state is wanted.  SoA: per lane, one contiguous 512 B access per component and wave
+// (load_state), and nothing to gather.  b: the lane's filter; an idle lane reads a valid one and
+// stores nothing.
+template <bool SOA, typename PT>
+struct StateMover {
+    const WaveTile &t;
+    double *X, *P;
+    int64_t batch;
+    double cx[4], cp[16];  // AoS: the wave's blocks of X and P, in block order
+
+    __device__ __forceinline__ StateMover(const WaveTile &tile, double *Xio, double *Pio, int64_t n)
+        : t(tile), X(Xio), P(Pio), batch(n) {}
+    __device__ __forceinline__ void gather() {
+        if constexpr (!SOA) {
+            t.gather(X, cx);
+            t.gather(P, cp);
+        }
+    }
+    __device__ __forceinline__ void to_lanes(int64_t b, double (&x)[4], Sym4T<PT> &S) const {
+        if constexpr (SOA) {
+            load_state<true>(X, P, b, batch, x, S);
+        } else {
+            double pv[16];
+            t.to_lanes(cx, x);
+            t.to_lanes(cp, pv);
+            S = sym_from16<PT>(pv);
+        }
+    }
+    __device__ __forceinline__ void store(int64_t b, const double (&x)[4], const Sym4T<PT> &S) const {
+        if constexpr (SOA) {
+            if (t.active()) store_state<true>(X, P, b, batch, x, S);
+        } else {
+            double pv[16];
+            sym_to16(S, pv);
+            t.store(X, x);
+            t.store(P, pv);
+        }
+    }
+};
 
 // Buffer resource of one plane row (raw, byte-addressed; gfx9 DWORD3 0x00020000)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void *row, int64_t bytes) {
@@ -163,19 +220,6 @@ struct RowCursor {
     }
 };
 
-// AoS P (full 4x4) <-> its upper triangle, for state moved through a WaveTile
-template <typename PT>
-__device__ __forceinline__ Sym4T<PT> sym_from16(const double (&p)[16]) {
-    return {(PT)p[0], (PT)p[1], (PT)p[2], (PT)p[3], (PT)p[5], (PT)p[6], (PT)p[7], (PT)p[10], (PT)p[11], (PT)p[15]};
-}
-template <typename PT>
-__device__ __forceinline__ void sym_to16(const Sym4T<PT> &S, double (&p)[16]) {
-    p[0] = S.a00; p[1] = S.a01; p[2] = S.a02; p[3] = S.a03;
-    p[4] = S.a01; p[5] = S.a11; p[6] = S.a12; p[7] = S.a13;
-    p[8] = S.a02; p[9] = S.a12; p[10] = S.a22; p[11] = S.a23;
-    p[12] = S.a03; p[13] = S.a13; p[14] = S.a23; p[15] = S.a33;
-}
-
 // |X|^2 of the state entering a launch.  After any record the state is unit (X /= |X|,
 // ExtendedKalmanFilter.py:79, or X = z from the normalised RK4 step) to within ~40 ulp of the
 // one-Newton-step rsqrt, and that is snapped to exactly 1: the stream kernel carries n2 = 1 as a
@@ -202,33 +246,44 @@ __device__ __forceinline__ double fma_rsub(double a, double b, double c) {
     return d;
 }
 
-// Per-launch constants of ekf_record_step.  MC = false: the covariance is carried as P itself;
-// MC = true (the multi-record stream loop): as N with P = rI + beta D N D, beta = sqrt(2) r,
+// The two forms of a record step (ekf_record_step below), as the LOOP argument of everything here
+constexpr bool kPlainForm = false, kLoopForm = true;
+
+// Per-launch constants of the FP64 ekf_record_step.  Plain form (LOOP = false): the covariance is
+// carried as P itself; loop form (LOOP = true): as N with P = rI + beta D N D, beta = sqrt(2) r,
 // D = diag(1, 1, -1, -1), so that the next N = -D (S^)^-1 D comes out of the Schur inverse of
 // innovation_cov_n's S^ with no update arithmetic (pekf_math.hpp).
-template <typename PT>
 struct StepK {
-    PT g2, r2;   // MC: 2g/beta, 2r/beta | P: 2g, 2r (innovation_cov_n / innovation_cov2)
-    PT rp, rr;   // P: r, 2r^2 (P = rI - 2r^2 (2S)^-1) | MC: r2 / 2 (innovation_cov_n_w), unused
-    double sy;   // Y's weight in the unnormalised X update: MC 1/sqrt(2), P 1/(2r)
+    double g2, r2;  // plain: 2g, 2r (innovation_cov2) | loop: 2g/beta, 2r/beta (innovation_cov_n)
+    double rp, rr;  // plain: r, 2r^2 (P = rI - 2r^2 (2S)^-1) | loop: r2 / 2 (innovation_cov_n's rbh), unused
+    double sy;      // Y's weight in the unnormalised X update: plain 1/(2r), loop 1/sqrt(2)
 };
-template <typename PT, bool MC>
-__device__ __forceinline__ StepK<PT> step_consts(double qs, double rs) {
-    const double g = 0.25 * qs;  // Jb Q Jb^T = (q/4)(|X|^2 I - X X^T)
-    if (MC) {
-        const double ib = 1.0 / (kSqrt2 * rs);
-        return {(PT)(2.0 * g * ib), (PT)(2.0 * rs * ib), (PT)(rs * ib), PT(0), 1.0 / kSqrt2};
+// ... and of the mixed-precision step (the f32 ekf_record_step below), which carries P in both forms
+struct StepKMixed {
+    double g2, ir;  // 2g, 1 / r
+    float r2, rp;   // 2r, r
+};
+template <bool MIXED, bool LOOP>
+__device__ __forceinline__ auto step_consts(double qs, double rs) {
+    if constexpr (MIXED) {
+        return StepKMixed{0.5 * qs, 1.0 / rs, (float)(2.0 * rs), (float)rs};
+    } else {
+        const double g = 0.25 * qs;  // Jb Q Jb^T = (q/4)(|X|^2 I - X X^T)
+        if constexpr (LOOP) {
+            const double ib = 1.0 / (kSqrt2 * rs);
+            return StepK{2.0 * g * ib, 2.0 * rs * ib, rs * ib, 0.0, 1.0 / kSqrt2};
+        } else {
+            return StepK{2.0 * g, 2.0 * rs, rs, 2.0 * (rs * rs), 0.5 / rs};
+        }
     }
-    return {(PT)(2.0 * g), (PT)(2.0 * rs), (PT)rs, (PT)(2.0 * (rs * rs)), 0.5 / rs};
 }
 
 // Wahba-skip: no Correction for this record (X = z, P = P- = S - rI)
-template <typename PT, bool MC>
-__device__ __forceinline__ void record_skip(double *x, const double *z, Sym4T<PT> &P, const Sym4T<PT> &S2,
-                                            const StepK<PT> &k) {
+template <bool LOOP>
+__device__ __forceinline__ void record_skip(double *x, const double *z, Sym4 &P, const Sym4 &S2, const StepK &k) {
     x[0] = z[0]; x[1] = z[1]; x[2] = z[2]; x[3] = z[3];
-    const PT hf = PT(0.5);
-    if (MC)  // D N D = (S - 2r I) / beta = S^/2 - rb I
+    const double hf = 0.5;
+    if (LOOP)  // D N D = (S - 2r I) / beta = S^/2 - rb I
         P = {fma(hf, S2.a00, -k.r2), hf * S2.a01, -hf * S2.a02, -hf * S2.a03, fma(hf, S2.a11, -k.r2),
              -hf * S2.a12, -hf * S2.a13, fma(hf, S2.a22, -k.r2), hf * S2.a23, fma(hf, S2.a33, -k.r2)};
     else
@@ -237,107 +292,109 @@ __device__ __forceinline__ void record_skip(double *x, const double *z, Sym4T<PT
 }
 
 // ---- Correction (ExtendedKalmanFilter.py:70-80) from S^-1 (Si) and Wahba's Y = v sc ----
-template <typename PT, bool MC>
-__device__ __forceinline__ void record_correct(double *x, const double *z, Sym4T<PT> &P, const Sym4T<PT> &Si,
-                                               const double *v, double sc, const StepK<PT> &k) {
-    // e = Y - z (MC: D e, whose last two components are z - Y)
-    const PT e0 = (PT)fma_sub(v[0], sc, z[0]), e1 = (PT)fma_sub(v[1], sc, z[1]);
-    const PT e2 = (PT)(MC ? fma_rsub(v[2], sc, z[2]) : fma_sub(v[2], sc, z[2]));
-    const PT e3 = (PT)(MC ? fma_rsub(v[3], sc, z[3]) : fma_sub(v[3], sc, z[3]));
-    // X = z + K e = Y - r S^-1 e (:77), normalised (:79): X ~ Y / (2r) - S^-1 e / 2, or (MC,
-    // S^-1 = -(2/beta) D Si D) X ~ Y / sqrt(2) + D Si D e
+template <bool LOOP>
+__device__ __forceinline__ void record_correct(double *x, const double *z, Sym4 &P, const Sym4 &Si, const double *v,
+                                               double sc, const StepK &k) {
+    // e = Y - z (loop form: D e, whose last two components are z - Y)
+    const double e0 = fma_sub(v[0], sc, z[0]), e1 = fma_sub(v[1], sc, z[1]);
+    const double e2 = LOOP ? fma_rsub(v[2], sc, z[2]) : fma_sub(v[2], sc, z[2]);
+    const double e3 = LOOP ? fma_rsub(v[3], sc, z[3]) : fma_sub(v[3], sc, z[3]);
+    // X = z + K e = Y - r S^-1 e (:77), normalised (:79): X ~ Y / (2r) - S^-1 e / 2, or (loop form,
+    // S^-1 = -(2/beta) D Si D) X ~ Y / sqrt(2) + D Si D e, left unnormalised
     const double u0 = Si.a00 * e0 + Si.a01 * e1 + Si.a02 * e2 + Si.a03 * e3;
     const double u1 = Si.a01 * e0 + Si.a11 * e1 + Si.a12 * e2 + Si.a13 * e3;
     const double u2 = Si.a02 * e0 + Si.a12 * e1 + Si.a22 * e2 + Si.a23 * e3;
     const double u3 = Si.a03 * e0 + Si.a13 * e1 + Si.a23 * e2 + Si.a33 * e3;
     const double sr = sc * k.sy;
-    const double x0 = fma(v[0], sr, MC ? u0 : -u0), x1 = fma(v[1], sr, MC ? u1 : -u1);
+    const double x0 = fma(v[0], sr, LOOP ? u0 : -u0), x1 = fma(v[1], sr, LOOP ? u1 : -u1);
     const double x2 = fma(v[2], sr, -u2), x3 = fma(v[3], sr, -u3);
-    if (MC) {
+    if (LOOP) {
         x[0] = x0; x[1] = x1; x[2] = x2; x[3] = x3;
     } else {
         const double in = rsqrt<true>(x0 * x0 + x1 * x1 + x2 * x2 + x3 * x3);
         x[0] = x0 * in; x[1] = x1 * in; x[2] = x2 * in; x[3] = x3 * in;
     }
     // P = P- - K P- = r K = r I - r^2 S^-1 = r I - (2 r^2) Si (:78)
-    if (MC) {
+    if (LOOP) {
         P = Si;  // P = rI + beta D N D: nothing to compute
     } else {
-        const PT rp = k.rp, rr = k.rr;
+        const double rp = k.rp, rr = k.rr;
         P = {rp - rr * Si.a00, -rr * Si.a01, -rr * Si.a02, -rr * Si.a03, rp - rr * Si.a11,
              -rr * Si.a12, -rr * Si.a13, rp - rr * Si.a22, -rr * Si.a23, rp - rr * Si.a33};
     }
 }
 
 // One record of main_file.py:42-45 -- Prediction(gyro, T) then Correction(mag, acc) -- on the
-// lane's state (x, P) in registers, in the world basis (Wf: the reference pair's Frame) or in the
-// reference frame's own basis (Wf: a RefW / RefWLazy, pekf_math.hpp); n2 = state_norm2 of x (1 for
-// every record after a launch's first).  gy = the gyro sample, dt_ns = T - previousT, missing: the
-// record has no magnetometer sample (record_skip).  Shared by the fused stream kernels, k_live and
-// the handle's per-record update, so all give bit-identical results for the same inputs.
-// In the reference frame's basis the measurement is Wahba's quaternion as a product of two plane
-// rotations (wahba_product_ref: the measured plane's normal to z, then the best turn about z), scaled
-// and flipped toward z by wahba_toward_from_product; in the world basis it is the matrix chain.
-// reload(acc, mag) re-reads the record's samples for the rare degenerate-Wahba fallback
-// (wahba_toward_from_product); it is not called on the common path.
-// MC (the multi-record loop): the covariance is carried as N (StepK), and X is left unnormalised,
-// X = x / |x| with |x| ~ 0.7: its norm folds into the next record's RK4 normalisation
-// (z = rk4(x) / |rk4(x)| whatever |x|) and Jb term (g (|X|^2 I - X X^T) = g I - (g / |x|^2) x x^T,
-// |X|^2 = 1 as state_norm2 snaps it), and 1/|x|^2 = in^2 kk comes from RK4's own rsqrt: 8 operations
-// instead of the 13 of normalising X.
-// LAZY: x arrives that way (n2 ignored); the caller normalises once at the end of the launch.
-// OM (the FP64 multi-record loop, inside OmodMode): the exact halvings fold into the instructions
-// that form the products (omod, pekf_math.hpp) -- the gyro is never scaled to h = w/2, and the
-// Newton steps of the rsqrt seeds need no separate multiply by 1/2: 9 VALU fewer per record, the
-// same values bit for bit.
-// PIN (with MC and OM): S^-1 depends only on the Prediction; it is held ahead of the rare fallback
-// branch, in the basic block of the Wahba chain, so that the two independent chains interleave (left
-// to itself the compiler sinks it past the branch, behind the Wahba chain).  Worth it where a SIMD
-// has one wave and the record's dependency chain is exposed (config 2: -2.3 %); neutral at 3 waves
-// per SIMD (config 3), where the other waves fill those gaps anyway (profiles/r2/ab_pin_schur/).
-// HOIST (the FP64 multi-record loop only): the Correction's state-independent half -- S^-1 and
-// Wahba's unnormalised quaternion q' -- is formed ahead of the missing-magnetometer branch, in the
-// Prediction's basic block (held there by an empty asm), so one block carries two independent
-// dependency chains (the Prediction's and the record's own); only q'.z, its scale and flip and the
-// update stay behind the branch.  For launches of at most one wave per SIMD (config 2), where nothing
-// else fills the chain's stalls (launch_run_multi selects it).
+// lane's state (x, P) in registers, all in FP64; n2 = state_norm2 of x (1 for every record after a
+// launch's first).  gy = the gyro sample, dt_ns = T - previousT, missing: the record has no magnetometer
+// sample (record_skip).  reload(acc, mag) re-reads the record's samples for the rare degenerate-Wahba
+// fallback; it is not called on the common path.  The step has two forms; the kernels that run the same
+// form share this code and give bit-identical results for the same inputs:
+//
+//            basis (Wf)                covariance  X after the record  halvings       rsqrt  callers
+//   plain    world (Frame)             P           normalised          multiplies     1      k_run_one, k_update
+//   loop     reference frame's (RefW,  N (StepK)   unnormalised        omod (inside   2      k_run (FP64), k_live
+//            RefWLazy; pekf_math.hpp)                                  OmodMode)
+//
+// Plain (LOOP = false), for the one-record launches, whose state comes from HBM and returns there every
+// record: the measurement is the matrix chain of wahba_quat_toward(const Frame &, ..).
+// Loop (LOOP = true), for the kernels that keep a filter in registers over many records, between
+// enter_ref_basis and from_ref_basis:
+//  - In the reference frame's basis the measurement is Wahba's quaternion as a product of two plane
+//    rotations (wahba_product_ref: the measured plane's normal to z, then the best turn about z), scaled
+//    and flipped toward z by wahba_toward_from_product.
+//  - The covariance is carried as N (StepK), and X is left unnormalised, X = x / |x| with |x| ~ 0.7:
+//    its norm folds into the next record's RK4 normalisation (z = rk4(x) / |rk4(x)| whatever |x|) and
+//    Jb term (g (|X|^2 I - X X^T) = g I - (g / |x|^2) x x^T, |X|^2 = 1 as state_norm2 snaps it), and
+//    1/|x|^2 = in^2 kk comes from RK4's own rsqrt: 8 operations instead of the 13 of normalising X.
+//  - The exact halvings fold into the instructions that form the products (omod, pekf_math.hpp) -- the
+//    gyro is never scaled to h = w/2, and the Newton steps of the rsqrt seeds need no separate multiply
+//    by 1/2: 9 VALU fewer per record, the same values bit for bit.  The caller opens the OmodMode.
+// The loop form's options:
+// LAZY: x arrives unnormalised (n2 ignored), as every record after a launch's first finds it; the
+// caller normalises once at the end of the launch.
+// PIN: S^-1 depends only on the Prediction; it is held ahead of the rare fallback branch, in the basic
+// block of the Wahba chain, so that the two independent chains interleave (left to itself the compiler
+// sinks it past the branch, behind the Wahba chain).  Worth it where a SIMD has one wave and the
+// record's dependency chain is exposed (config 2: -2.3 %); neutral at 3 waves per SIMD (config 3),
+// where the other waves fill those gaps anyway (profiles/r2/ab_pin_schur/).
+// HOIST: the Correction's state-independent half -- S^-1 and Wahba's unnormalised quaternion q' -- is
+// formed ahead of the missing-magnetometer branch, in the Prediction's basic block (held there by an
+// empty asm), so one block carries two independent dependency chains (the Prediction's and the
+// record's own); only q'.z, its scale and flip and the update stay behind the branch.  For launches of
+// at most one wave per SIMD (config 2), where nothing else fills the chain's stalls (launch_run_multi
+// selects it).
 // PIN and HOIST move instructions only: the arithmetic is the same, bit for bit.
-template <typename PT, bool MC = false, bool LAZY = false, bool OM = false, bool PIN = false, bool HOIST = false,
-          typename Ref, typename Reload>
-__device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> &P, const Ref &Wf, const StepK<PT> &k,
+template <bool LOOP, bool LAZY = false, bool PIN = false, bool HOIST = false, typename Ref, typename Reload>
+__device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4 &P, const Ref &Wf, const StepK &k,
                                                 const double *gy, double dt_ns, bool missing,
                                                 const double *acc, const double *mag, const Reload &reload) {
-    static_assert(!OM || (MC && std::is_same<PT, double>::value), "omod form: FP64 multi-record loop only");
-    static_assert(!HOIST || OM, "hoisted form: FP64 multi-record loop only");
-    constexpr int F = OM ? 2 : 1;  // rsqrt form
+    static_assert(LOOP || !(LAZY || PIN || HOIST), "LAZY, PIN and HOIST are options of the loop form");
+    static_assert(LOOP != std::is_same<Ref, Frame>::value, "plain form: world basis; loop form: the reference frame's");
+    constexpr int F = LOOP ? 2 : 1;  // rsqrt form
     // ---- Prediction (ExtendedKalmanFilter.py:58-68) ----
-    const double n2x = LAZY ? x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3] : n2;
-    double z[4], kk, irk;
-    Sym4T<PT> S2;
-    if constexpr (OM) {
+    double z[4];
+    Sym4 S2;
+    if constexpr (LOOP) {
+        const double n2x = LAZY ? x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3] : n2;
+        double kk, irk;
         // th2x2 = 2 |h|^2 = |w|^2 / 2 (0.5*Omega(w) = Omega(h), h = w/2)
         const double th2x2 = fma_half(gy[2], gy[2], fma(gy[1], gy[1], gy[0] * gy[0]));
         rk4_closed_w(x, n2x, dt_ns, gy, th2x2, z, kk, irk);                  // (:62)
         const double g2x = LAZY ? ((irk * irk) * kk) * k.g2 : k.g2;           // 2g / |x|^2
-        S2 = innovation_cov_n_w(P, gy, th2x2, x, LAZY ? 1.0 : n2, k.g2, k.r2, k.rp, g2x);
+        S2 = innovation_cov_n(P, gy, th2x2, x, LAZY ? 1.0 : n2, k.g2, k.r2, k.rp, g2x);
     } else {
         const double hw[3] = {0.5 * gy[0], 0.5 * gy[1], 0.5 * gy[2]};  // 0.5*Omega(w) = Omega(w/2)
         const double th2 = hw[0] * hw[0] + hw[1] * hw[1] + hw[2] * hw[2];
-        const PT hp[3] = {(PT)hw[0], (PT)hw[1], (PT)hw[2]};
-        const PT wp[3] = {(PT)gy[0], (PT)gy[1], (PT)gy[2]};
-        const PT xp[4] = {(PT)x[0], (PT)x[1], (PT)x[2], (PT)x[3]};
-        rk4_closed(x, n2x, dt_ns, hw, th2, z, kk, irk);                    // (:62)
-        const PT g2x = LAZY ? (PT)((irk * irk) * kk) * k.g2 : k.g2;         // 2g / |x|^2
-        const PT n2p = LAZY ? PT(1) : (PT)n2;
+        rk4_closed(x, n2, dt_ns, hw, th2, z);                              // (:62)
         // S2 = 2S, S = P- + rI with P- = A P A^T + Jb Q Jb^T, Jb from the prior X (:60-61, :63).
         // Exactly twice S (see innovation_cov2), so every result below is bit-identical to the
         // undoubled recursion: (2S)^-1 = S^-1/2, and the constants absorb the factor.
-        S2 = MC ? innovation_cov_n<PT>(P, hp, wp, (PT)th2, xp, n2p, k.g2, k.r2, g2x)
-                : innovation_cov2<PT>(P, hp, wp, (PT)th2, xp, n2p, k.g2, k.r2, g2x);
+        S2 = innovation_cov2(P, hw, gy, th2, x, n2, k.g2, k.r2, k.g2);
     }
 
     if constexpr (HOIST) {
-        const Sym4T<PT> Si = spd_inverse_schur<PT, true, MC>(S2);
+        const Sym4 Si = spd_inverse_schur<LOOP>(S2);
         const double ka = fabs(acc[2]);              // (:71)
         double qm[4];
         wahba_product_ref<F>(Wf, acc, mag, ka, 1.0 - ka, qm);
@@ -345,36 +402,29 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> 
                      "v"(Si.a13), "v"(Si.a22), "v"(Si.a23), "v"(Si.a33), "v"(qm[0]), "v"(qm[1]), "v"(qm[2]),
                      "v"(qm[3]));
         if (missing) {
-            record_skip<PT, MC>(x, z, P, S2, k);
+            record_skip<LOOP>(x, z, P, S2, k);
         } else {
             double v[4], sc;
             wahba_toward_from_product<F>(Wf, qm, 1.0 - ka, z, v, sc, reload);  // Wahba.py:8-47 + the flip of :73-75
-            record_correct<PT, MC>(x, z, P, Si, v, sc, k);
+            record_correct<LOOP>(x, z, P, Si, v, sc, k);
         }
         return;
     }
     if (missing) {
-        record_skip<PT, MC>(x, z, P, S2, k);
+        record_skip<LOOP>(x, z, P, S2, k);
     } else {
-        // K = P- S^-1 = I - r S^-1  (:64-66); Si = S^-1 / 2, or (MC) the next N = -D (S^)^-1 D
-        const Sym4T<PT> Si = spd_inverse_schur<PT, true, MC>(S2);
+        // K = P- S^-1 = I - r S^-1  (:64-66); Si = S^-1 / 2, or (loop form) the next N = -D (S^)^-1 D
+        const Sym4 Si = spd_inverse_schur<LOOP>(S2);
         const double ka = fabs(acc[2]);              // (:71)
         double v[4], sc;
         auto pin = [&] {
-            if constexpr (PIN && MC && OM)
+            if constexpr (PIN)
                 asm volatile("" ::"v"(Si.a00), "v"(Si.a01), "v"(Si.a02), "v"(Si.a03), "v"(Si.a11), "v"(Si.a12),
                              "v"(Si.a13), "v"(Si.a22), "v"(Si.a23), "v"(Si.a33));
         };
         // Wahba.py:8-47 + the flip of :73-75: Y = v sc
-        if constexpr (std::is_same<Ref, Frame>::value) {
-            Frame Vf;
-            // ka = |acc_z| >= 0, so wahba_sign(ka, km) is the sign of km = 1 - ka (never -0)
-            make_frame<F>(acc, mag, Vf, 1.0 - ka);
-            wahba_quat_toward<F>(Wf, Vf, ka, 1.0 - ka, z, v, sc, reload, pin);
-        } else {
-            wahba_quat_toward<F>(Wf, acc, mag, ka, 1.0 - ka, z, v, sc, reload, pin);
-        }
-        record_correct<PT, MC>(x, z, P, Si, v, sc, k);
+        wahba_quat_toward<F>(Wf, acc, mag, ka, 1.0 - ka, z, v, sc, reload, pin);
+        record_correct<LOOP>(x, z, P, Si, v, sc, k);
     }
 }
 
@@ -392,20 +442,17 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<PT> 
 // inverse and the product P- S^-1 are f32.  The covariance is carried as P in every launch shape (in the
 // multi-record loop in the reference frame's basis).  P e is formed in FP64 from the f32 P, e = Y - z
 // stays FP64, and RK4, Wahba and the normalisation are the FP64 step's.
-// NORM = false (the multi-record loop) leaves X = z + K e unnormalised, as the FP64 loop does:
-// LAZY is ekf_record_step's.
-struct StepKMixed {
-    double g2, ir;  // 2g, 1 / r
-    float r2, rp;   // 2r, r
-};
-__device__ __forceinline__ StepKMixed step_consts_mixed(double qs, double rs) {
-    return {0.5 * qs, 1.0 / rs, (float)(2.0 * rs), (float)rs};
-}
-template <bool LAZY, bool NORM, typename Ref, typename Reload>
-__device__ __forceinline__ void ekf_record_step_mixed(double *x, double n2, Sym4T<float> &P, const Ref &Wf,
-                                                      const StepKMixed &k, const double *gy, double dt_ns,
-                                                      bool missing, const double *acc, const double *mag,
-                                                      const Reload &reload) {
+// It is ekf_record_step's overload for an f32 covariance and a StepKMixed, so a kernel writes one call
+// for either precision.  LOOP and LAZY are the FP64 step's: LOOP = false normalises X every record;
+// LOOP = true (the multi-record loop, in the reference frame's basis) leaves X = z + K e unnormalised.
+// No omod, so rsqrt form 1 in both.  It has none of the FP64 loop's schedules: PIN and HOIST are named
+// only so that k_run can hand its own flags to either overload, and must be false.
+template <bool LOOP, bool LAZY = false, bool PIN = false, bool HOIST = false, typename Ref, typename Reload>
+__device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4T<float> &P, const Ref &Wf,
+                                                const StepKMixed &k, const double *gy, double dt_ns, bool missing,
+                                                const double *acc, const double *mag, const Reload &reload) {
+    static_assert(LOOP || !LAZY, "LAZY is an option of the loop form");
+    static_assert(!PIN && !HOIST, "PIN and HOIST are schedules of the FP64 loop form");
     // ---- Prediction (ExtendedKalmanFilter.py:58-68) ----
     const double n2x = LAZY ? x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3] : n2;
     const double hw[3] = {0.5 * gy[0], 0.5 * gy[1], 0.5 * gy[2]};  // 0.5*Omega(w) = Omega(w/2)
@@ -414,7 +461,7 @@ __device__ __forceinline__ void ekf_record_step_mixed(double *x, double n2, Sym4
     rk4_closed(x, n2x, dt_ns, hw, th2, z, kk, irk);                      // (:62)
     const double g2x = LAZY ? ((irk * irk) * kk) * k.g2 : k.g2;          // 2g / |x|^2
     const Sym4 Pd = {P.a00, P.a01, P.a02, P.a03, P.a11, P.a12, P.a13, P.a22, P.a23, P.a33};
-    const Sym4 Md = innovation_cov2<double>(Pd, hw, gy, th2, x, LAZY ? 1.0 : n2, k.g2, 0.0, g2x);  // 2P- (:61)
+    const Sym4 Md = innovation_cov2(Pd, hw, gy, th2, x, LAZY ? 1.0 : n2, k.g2, 0.0, g2x);  // 2P- (:61)
     const Sym4T<float> M2 = {(float)Md.a00, (float)Md.a01, (float)Md.a02, (float)Md.a03, (float)Md.a11,
                              (float)Md.a12, (float)Md.a13, (float)Md.a22, (float)Md.a23, (float)Md.a33};
     if (missing) {  // Wahba-skip: X = z, P = P-
@@ -426,17 +473,11 @@ __device__ __forceinline__ void ekf_record_step_mixed(double *x, double n2, Sym4
     }
     Sym4T<float> S2 = M2;  // 2S = 2P- + 2rI (:63)
     S2.a00 += k.r2; S2.a11 += k.r2; S2.a22 += k.r2; S2.a33 += k.r2;
-    const Sym4T<float> Si = spd_inverse_schur<float, true, false>(S2);    // S^-1 / 2
+    const Sym4T<float> Si = spd_inverse_schur(S2);                        // S^-1 / 2
     // ---- Correction (ExtendedKalmanFilter.py:70-80) ----
     const double ka = fabs(acc[2]);  // (:71)
     double v[4], sc;                 // Wahba.py:8-47 + the flip of :73-75: Y = v sc
-    if constexpr (std::is_same<Ref, Frame>::value) {
-        Frame Vf;
-        make_frame<1>(acc, mag, Vf, 1.0 - ka);
-        wahba_quat_toward<1>(Wf, Vf, ka, 1.0 - ka, z, v, sc, reload);
-    } else {
-        wahba_quat_toward<1>(Wf, acc, mag, ka, 1.0 - ka, z, v, sc, reload);
-    }
+    wahba_quat_toward<1>(Wf, acc, mag, ka, 1.0 - ka, z, v, sc, reload);
     P = sym_product_upper(M2, Si, k.rp);  // P = P- - K P- = r K (:66, :78)
     const double e0 = fma_sub(v[0], sc, z[0]), e1 = fma_sub(v[1], sc, z[1]);
     const double e2 = fma_sub(v[2], sc, z[2]), e3 = fma_sub(v[3], sc, z[3]);
@@ -448,7 +489,7 @@ __device__ __forceinline__ void ekf_record_step_mixed(double *x, double n2, Sym4
     const double u3 = p03 * e0 + p13 * e1 + p23 * e2 + p33 * e3;
     const double x0 = fma(u0, k.ir, z[0]), x1 = fma(u1, k.ir, z[1]);      // X = z + K e (:77)
     const double x2 = fma(u2, k.ir, z[2]), x3 = fma(u3, k.ir, z[3]);
-    if (NORM) {  // (:79)
+    if (!LOOP) {  // (:79)
         const double in = rsqrt<true>(x0 * x0 + x1 * x1 + x2 * x2 + x3 * x3);
         x[0] = x0 * in; x[1] = x1 * in; x[2] = x2 * in; x[3] = x3 * in;
     } else {
@@ -466,7 +507,7 @@ __device__ __forceinline__ void to_ref_basis(const double *qw, double *x, Sym4T<
     qmul_left<true>(qw, x, xw);
     x[0] = xw[0]; x[1] = xw[1]; x[2] = xw[2]; x[3] = xw[3];
     P = sym_rotate<true>(qw, P);
-    if constexpr (std::is_same<PT, double>::value) {  // the mixed loop carries P itself (ekf_record_step_mixed)
+    if constexpr (std::is_same<PT, double>::value) {  // the mixed loop carries P itself (the f32 ekf_record_step)
         const PT ib = (PT)(1.0 / (kSqrt2 * rs)), rp = (PT)rs;
         P = {(P.a00 - rp) * ib, P.a01 * ib, -P.a02 * ib, -P.a03 * ib, (P.a11 - rp) * ib,
              -P.a12 * ib, -P.a13 * ib, (P.a22 - rp) * ib, P.a23 * ib, (P.a33 - rp) * ib};
@@ -533,7 +574,7 @@ __device__ __forceinline__ void from_ref_basis(const RW &Wr, double *x, Sym4T<PT
 // fraction, no escape word; every record carries a magnetometer sample, as a log's always does).
 // MIXED = false: every operation in FP64 (the headline path).
 // MIXED = true (opt-in, PEKF_RUN_MIXED_PRECISION): the covariance recursion (P-, S^-1, K, P)
-// in FP32 while RK4, Wahba, R->q and the X update stay FP64 (ekf_record_step_mixed).
+// in FP32 while RK4, Wahba, R->q and the X update stay FP64 (the f32 ekf_record_step).
 // COUNTS: filter b applies only its first counts[b] records of the launch (a separate
 // instantiation so the uniform-length path carries no per-step lane predicate).
 // PIN: the Schur-inverse-first schedule of the multi-record loop (ekf_record_step, launch_run_multi).
@@ -604,12 +645,8 @@ __global__ __launch_bounds__(kRunBlock) PEKF_RUN_ATTR void k_run(int64_t batch, 
                 missing = (word & PEKF_MISSING_MAG_BIT) != 0;
             }
             auto reload = [&](double *a, double *m) { rows.reload(kLag, a, m); };  // rare: this record again
-            if constexpr (MIXED)
-                ekf_record_step_mixed<decltype(lazy)::value, false>(x, n2, P, Wr, step_consts_mixed(qs, rs), gy, dtn,
-                                                                    missing, acc, mag, reload);
-            else
-                ekf_record_step<PT, true, decltype(lazy)::value, true, PIN, HOIST>(
-                    x, n2, P, Wr, step_consts<PT, true>(qs, rs), gy, dtn, missing, acc, mag, reload);
+            ekf_record_step<kLoopForm, decltype(lazy)::value, PIN, HOIST>(
+                x, n2, P, Wr, step_consts<MIXED, kLoopForm>(qs, rs), gy, dtn, missing, acc, mag, reload);
         }
         if (TRAJ) {
             // a filter with no records in this launch (COUNTS) repeats its stored X unchanged

@@ -2,7 +2,7 @@
 
 The mixed launches hold the covariance in f32 and run its recursion in the kernels' own algebra (2P- by trace
 butterflies, formed in FP64 and rounded once; in f32 S inverted by 2x2 blocks and P = r P- S^-1;
-X = z + P e / r: ekf_record_step_mixed; until these tests the
+X = z + P e / r: ekf_record_step's f32 overload; until these tests the
 FP64 step's differences from r, K = I - r S^-1, P = rI - r^2 S^-1, whose f32 error grows like r / q and
 missed the rule from q / r = 0.15 down).  The yardstick is the reference's own
 algebra with the covariance in f32, tests/mixed_numpy.run_filter_pt(np.float32): NumPy and LAPACK, no code
