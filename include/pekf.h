@@ -339,6 +339,38 @@ int pekf_live_traj_dev(int64_t batch, int64_t n_events, const void *ev_planes, c
                        int32_t *counts, double *refs, uint32_t flags, double *traj, double *traj_dt,
                        int64_t traj_rows, int *dev_error, void *stream);
 
+/* A live session fed in chunks: pekf_live_traj_dev on the next n_events rows of the same filters' streams,
+ * leaving in `state` what the next call needs to continue -- however a session's events are cut into calls,
+ * every output (X, P, refs, the summed counts, the trajectory rows and their dts in order) has the bits of the
+ * one call over all of them.  resume == 0 starts a session: the front-end from init / t_init / alpha and the
+ * filter from X / P, exactly as pekf_live_ext_dev; resume != 0 continues it from `state`.
+ *   What carries over, in `state`: the front-end's half-assembled record (the pending samples, their times and
+ * flags), its low-pass outputs and its clocks, and the filter as the kernel's loop holds it (the unnormalised
+ * state in the reference pair's basis, the covariance factor, the number of records applied so far).  What does
+ * not: the record queue (every launch applies all the records it completes before it ends), and init, t_init,
+ * alpha, q, r, which every call of a session must pass unchanged (t_init is read only with resume == 0).
+ *   X / P: written at the end of every call for the filters that applied a record in it (the server's X_k of
+ * their last record), left alone for the others; counts[b] and the trajectory rows count within the call.  With
+ * resume != 0 X and P are NOT read: the state holds the filter, so what the caller writes to X / P between two
+ * chunks does not reach it (start a new session, resume == 0, to do that).
+ *   state: a device buffer of pekf_live_state_bytes(batch, flags) bytes, 16-byte aligned, required.  Its layout
+ * is private and belongs to one event form -- f32 events (flags 0 or PEKF_EV_TIME_EVENTS, which may differ from
+ * chunk to chunk) or FP64 events (PEKF_EV_F64_EVENTS) -- and one batch: it is indexed by the filter's number among
+ * `batch`, so it cannot be resumed with another batch or the other form, but its bytes may be copied to another
+ * buffer or device.  PEKF_EV_F32_RECORDS is refused (PEKF_ERR_INVALID): it exists to equal the one-shot split
+ * pipeline.  Every other check is pekf_live_traj_dev's.  n_events == 0 is legal: with resume == 0 it writes the
+ * fresh state, with resume != 0 it changes nothing; counts are 0 either way. */
+int pekf_live_resume_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                         const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
+                         int32_t *counts, double *refs, uint32_t flags, void *state, int resume,
+                         double *traj, double *traj_dt, int64_t traj_rows, int *dev_error, void *stream);
+/* The bytes of a session state for `batch` filters and these flags (host only, no device needed); < 0: flags
+ * pekf_live_resume_dev refuses, or a negative batch.  The one entry that returns a size, not a status: 64 bits,
+ * int64_t's width on every platform this library builds for, spelled so that the declaration reads
+ * `int pekf_...(` at the start of a line like every other entry's (tests/test_capi.py lists the ABI by that). */
+long long
+int pekf_live_state_bytes(int64_t batch, uint32_t flags);
+
 /* Phase 2 of the server's Parser (KFS/Parser.cpp:36-58,84-140; KFS/InitialValues.cpp) on the device: per
  * filter, the mean and sample variance of the first n_avg (the server: 100) samples of each sensor type,
  * and the time phase 3 continues from.  Events as for pekf_frontend_dev (ev_planes [n_events][batch], word

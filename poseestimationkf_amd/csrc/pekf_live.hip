@@ -34,21 +34,9 @@ static int launch_live(int64_t batch, int64_t n_events, const void *ev_planes, c
                        const int64_t *t_init, double alpha, double *X, double *P, double q, double r, int32_t *counts,
                        double *refs, uint32_t flags, double *traj, double *traj_dt, int64_t traj_rows, int *dev_error,
                        void *stream) {
-    PEKF_CHECK_ARG(batch >= 0 && n_events >= 0, "negative size");
-    PEKF_CHECK_ARG((flags & ~(PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS | PEKF_EV_F64_EVENTS)) == 0, "unknown flags");
-    const bool ev64 = (flags & PEKF_EV_F64_EVENTS) != 0;
-    PEKF_CHECK_ARG(!ev64 || (flags & (PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS)) == 0,
-                   "PEKF_EV_F64_EVENTS takes no other flag (FP64 events carry their times; their records are FP64)");
-    PEKF_CHECK_ARG(traj_rows >= 0 && traj_rows < ((int64_t)1 << 31), "traj_rows must be >= 0 and < 2^31");
-    PEKF_CHECK_ARG(traj_rows == 0 || (traj && (uintptr_t)traj % 16 == 0),
-                   "traj must be a 16-byte aligned pointer when traj_rows > 0");
-    PEKF_CHECK_ARG(traj_rows == 0 || (uintptr_t)traj_dt % 8 == 0, "misaligned traj_dt");
+    if (int st = check_live_flags(batch, n_events, flags, traj, traj_dt, traj_rows)) return st;
     if (batch == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(batch < ((int64_t)1 << 28), "batch must be < 2^28 filters per launch");
-    PEKF_CHECK_ARG(n_events < ((int64_t)1 << 30), "n_events must be < 2^30 per launch");
-    PEKF_CHECK_ARG(ev_planes && init && t_init && X && P && counts && refs, "null pointer");
-    PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
-    PEKF_CHECK_ARG(r > 0.0, "r must be > 0 (S = P- + rI must be SPD)");
+    if (int st = check_live_launch(batch, n_events, ev_planes, init, t_init, X, P, r, counts, refs)) return st;
     (void)dev_error;  // every record's dt is applied (escaped ones from the queue's side entries)
     if (traj_rows > 0)  // the TRAJ twins: pekf_live_traj.hip
         return launch_live_traj(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, traj,

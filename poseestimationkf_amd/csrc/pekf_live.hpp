@@ -1,5 +1,6 @@
 // pekf_live.hpp -- k_live, the fused front-end + filter kernel, and its record queue (see pekf_live.hip,
-// which instantiates the kernels without trajectory output; pekf_live_traj.hip instantiates their TRAJ twins).
+// which instantiates the kernels without trajectory output; pekf_live_traj.hip instantiates their TRAJ twins,
+// pekf_live_resume.hip the resumable kernels of a session fed in chunks).
 #pragma once
 #include "pekf_phase3.hpp"
 #include "pekf_step.hpp"
@@ -214,6 +215,104 @@ struct RecordQueue : Slots<Q> {
     }
 };
 
+// A resumable launch's session state (k_live<..., RESUME>): what a lane holds between two event blocks, so that
+// the next launch on the same filters' next events continues as one launch over all of them would.  The
+// front-end: every member Phase3T::start sets but the phase-2 means and alpha / beta (remade from init and
+// alpha) and pend / p (nothing is pending after a whole block, and a launch ends on one).  The filter as the loop
+// holds it: the unnormalised reference-basis x, the ten entries of N, and `total`, the records the filter has
+// applied since the session began (the first of them alone takes the eager step).  The record queue is empty at
+// a launch's end, so nothing of it is carried.
+//
+// One device buffer of filter-minor planes of 16 B per lane, [plane][batch]: a wave's load or store of a plane
+// is one contiguous 1 KB access.  Two doubles pair up in a plane, four f32 samples in one; the five flags and
+// `total` share the last double's plane.  f32 events: 27 doubles + {flags, total} in 14 planes and the 15 f32
+// sample words in 4, 288 B per filter.  FP64 events: 41 doubles + {flags, total} in 21 planes, 336 B (their
+// running clock t is never read: FP64 events carry their times).  Read once before the event loop, written
+// once after it.
+template <bool EV64>
+struct LiveState {
+    using Fe = Phase3T<std::conditional_t<EV64, V3, F3>>;
+    static constexpr int kDoubles = EV64 ? 42 : 28;                 // the last one holds {flags, total}
+    static constexpr int kPlanes = kDoubles / 2 + (EV64 ? 0 : 4);   // f32 events: 4 float4 planes of samples
+    static constexpr int kBytes = 16 * kPlanes;                     // per filter
+
+    template <bool LOAD, typename T>
+    static __device__ __forceinline__ void mv(T &member, double &word) {
+        if constexpr (LOAD)
+            member = word;
+        else
+            word = member;
+    }
+    // the doubles in their order in the planes, to (LOAD = false) or from d
+    template <bool LOAD>
+    static __device__ __forceinline__ void doubles(Fe &fe, double *x, Sym4T<double> &N, double (&d)[kDoubles]) {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mv<LOAD>(x[i], d[k++]);
+        mv<LOAD>(N.a00, d[k++]); mv<LOAD>(N.a01, d[k++]); mv<LOAD>(N.a02, d[k++]); mv<LOAD>(N.a03, d[k++]);
+        mv<LOAD>(N.a11, d[k++]); mv<LOAD>(N.a12, d[k++]); mv<LOAD>(N.a13, d[k++]); mv<LOAD>(N.a22, d[k++]);
+        mv<LOAD>(N.a23, d[k++]); mv<LOAD>(N.a33, d[k++]);
+        mv<LOAD>(fe.lpf_acc.x, d[k++]); mv<LOAD>(fe.lpf_acc.y, d[k++]); mv<LOAD>(fe.lpf_acc.z, d[k++]);
+        mv<LOAD>(fe.lpf_mag.x, d[k++]); mv<LOAD>(fe.lpf_mag.y, d[k++]); mv<LOAD>(fe.lpf_mag.z, d[k++]);
+        mv<LOAD>(fe.t_acc0, d[k++]); mv<LOAD>(fe.t_mag0, d[k++]); mv<LOAD>(fe.prev_t, d[k++]);
+        mv<LOAD>(fe.t_acc1, d[k++]); mv<LOAD>(fe.t_mag1, d[k++]); mv<LOAD>(fe.t_gyro, d[k++]);
+        if constexpr (EV64) {
+            mv<LOAD>(fe.acc0.x, d[k++]); mv<LOAD>(fe.acc0.y, d[k++]); mv<LOAD>(fe.acc0.z, d[k++]);
+            mv<LOAD>(fe.mag0.x, d[k++]); mv<LOAD>(fe.mag0.y, d[k++]); mv<LOAD>(fe.mag0.z, d[k++]);
+            mv<LOAD>(fe.acc1.x, d[k++]); mv<LOAD>(fe.acc1.y, d[k++]); mv<LOAD>(fe.acc1.z, d[k++]);
+            mv<LOAD>(fe.mag1.x, d[k++]); mv<LOAD>(fe.mag1.y, d[k++]); mv<LOAD>(fe.mag1.z, d[k++]);
+            mv<LOAD>(fe.gyro.x, d[k++]); mv<LOAD>(fe.gyro.y, d[k++]); mv<LOAD>(fe.gyro.z, d[k++]);
+        } else {
+            mv<LOAD>(fe.t, d[k++]);
+        }
+    }
+    static __device__ __forceinline__ double2 *plane(void *state, int64_t batch, int64_t b, int p) {
+        return reinterpret_cast<double2 *>(state) + ((int64_t)p * batch + b);
+    }
+
+    static __device__ __forceinline__ void load(void *state, int64_t batch, int64_t b, Fe &fe, double *x,
+                                                Sym4T<double> &N, int32_t &total) {
+        double d[kDoubles];
+#pragma unroll
+        for (int p = 0; p < kDoubles / 2; ++p) {
+            const double2 v = *plane(state, batch, b, p);
+            d[2 * p] = v.x;
+            d[2 * p + 1] = v.y;
+        }
+        doubles<true>(fe, x, N, d);
+        const uint32_t flags = (uint32_t)__double2loint(d[kDoubles - 1]);
+        total = __double2hiint(d[kDoubles - 1]);
+        fe.acc0_mean = flags & 1u; fe.mag0_mean = flags & 2u;
+        fe.gyro_set = flags & 4u; fe.acc1_set = flags & 8u; fe.mag1_set = flags & 16u;
+        if constexpr (!EV64) {
+            float4 s[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) s[p] = *reinterpret_cast<const float4 *>(plane(state, batch, b, kDoubles / 2 + p));
+            fe.acc0 = {s[0].x, s[0].y, s[0].z}; fe.mag0 = {s[0].w, s[1].x, s[1].y};
+            fe.acc1 = {s[1].z, s[1].w, s[2].x}; fe.mag1 = {s[2].y, s[2].z, s[2].w};
+            fe.gyro = {s[3].x, s[3].y, s[3].z};
+        }
+    }
+    static __device__ __forceinline__ void store(void *state, int64_t batch, int64_t b, Fe &fe, double *x,
+                                                 Sym4T<double> &N, int32_t total) {
+        double d[kDoubles];
+        doubles<false>(fe, x, N, d);
+        const uint32_t flags = (fe.acc0_mean ? 1u : 0u) | (fe.mag0_mean ? 2u : 0u) | (fe.gyro_set ? 4u : 0u) |
+                               (fe.acc1_set ? 8u : 0u) | (fe.mag1_set ? 16u : 0u);
+        d[kDoubles - 1] = __hiloint2double(total, (int)flags);
+#pragma unroll
+        for (int p = 0; p < kDoubles / 2; ++p) *plane(state, batch, b, p) = make_double2(d[2 * p], d[2 * p + 1]);
+        if constexpr (!EV64) {
+            const float4 s[4] = {make_float4(fe.acc0.x, fe.acc0.y, fe.acc0.z, fe.mag0.x),
+                                 make_float4(fe.mag0.y, fe.mag0.z, fe.acc1.x, fe.acc1.y),
+                                 make_float4(fe.acc1.z, fe.mag1.x, fe.mag1.y, fe.mag1.z),
+                                 make_float4(fe.gyro.x, fe.gyro.y, fe.gyro.z, 0.f)};
+#pragma unroll
+            for (int p = 0; p < 4; ++p) *reinterpret_cast<float4 *>(plane(state, batch, b, kDoubles / 2 + p)) = s[p];
+        }
+    }
+};
+
 // TE: the event planes may hold time events (Phase3::event).  R64: records keep their FP64 acc / mag
 // (SlotsLpf); otherwise they are the f32 stream records pekf_frontend_dev writes (SlotsF32).
 // EV64: FP64 events (PEKF_EV_F64_EVENTS, double4 planes: the server's own sample values), records all
@@ -225,12 +324,21 @@ struct RecordQueue : Slots<Q> {
 // number: lanes complete records at different events, so a wave's 64 stores fall in up to 64 rows.  Nothing
 // else is written (rows >= counts[b], every row of a filter that is not ready or has no record).  The
 // kernels without TRAJ read none of the three arguments.
-template <bool TE, bool R64, bool EV64 = false, bool TRAJ = false>
+// RESUME: a session fed in several launches (pekf_live_resume_dev).  The lane's session state (LiveState) is
+// stored in `state` after the event loop -- the raw x and N, before from_ref_basis touches them -- and, with
+// resume != 0, loaded from it before the loop in place of the fresh start (fe.start, load_state and
+// enter_ref_basis's rotation; Wr depends on the references alone and is made from init as ever).  The first
+// record of a launch takes the eager form only if the filter has applied none in the whole session, so every
+// record is applied by the call the single launch makes for it and any cutting of a session's events into
+// launches gives the single launch's bits.  X / P are written, and counts[b] and the trajectory rows count, per
+// launch.  The kernels without RESUME read neither argument.
+template <bool TE, bool R64, bool EV64 = false, bool TRAJ = false, bool RESUME = false>
 __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 ? PEKF_LIVE_EV64_WAVES : 2))) void k_live(
     int64_t batch, int64_t n_events, const std::conditional_t<EV64, double4, float4> *__restrict__ ev,
     const double *__restrict__ init, const int64_t *__restrict__ t_init, double alpha, double qs, double rs,
     double *__restrict__ Xio, double *__restrict__ Pio, int32_t *__restrict__ counts, double *__restrict__ refs,
-    double *__restrict__ traj, double *__restrict__ traj_dt, int32_t traj_rows) {
+    double *__restrict__ traj, double *__restrict__ traj_dt, int32_t traj_rows, void *__restrict__ state,
+    int32_t resume) {
     using EvT = std::conditional_t<EV64, double4, float4>;
     constexpr int kRing = EV64 ? PEKF_LIVE_RING64 : PEKF_LIVE_RING, kFlush = 3, kQuorum = PEKF_LIVE_QUORUM;
     constexpr int kQueue = EV64 ? PEKF_LIVE_QUEUE_EV64 : R64 ? PEKF_LIVE_QUEUE64 : PEKF_LIVE_QUEUE;
@@ -259,11 +367,26 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     make_frame<true>(rf, rf + 3, Wf);
     double x[4];
     Sym4T<double> P;
-    load_state<false>(Xio, Pio, b, batch, x, P);
+    if constexpr (RESUME) {
+        // resumed: the state holds the filter (what enter_ref_basis rotates below is then replaced)
+        if (resume) {
+            x[0] = 1.0; x[1] = x[2] = x[3] = 0.0;
+            P = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 1.0};
+        } else {
+            load_state<false>(Xio, Pio, b, batch, x, P);
+        }
+    } else {
+        load_state<false>(Xio, Pio, b, batch, x, P);
+    }
     // (TRAJ: q_W held for the rows, as k_run's TRAJ kernels hold it; converting late needs it only at the end)
     constexpr bool kLate = TRAJ && PEKF_LIVE_TRAJ_LATE;
     const auto Wr = enter_ref_basis<TRAJ && !kLate>(Wf, refs + 6 * b, false, x, P, rs);
     const StepK kc = step_consts<false, kLoopForm>(qs, rs);
+    int32_t applied0 = 0;  // RESUME: the records applied in the session's earlier launches
+    if constexpr (RESUME) {
+        if (resume) LiveState<EV64>::load(state, batch, b, fe, x, P, applied0);
+    }
+    const bool fresh = applied0 == 0;
 
     using Queue = std::conditional_t<EV64, RecordQueue<SlotsF64, kQueue>,
                                      std::conditional_t<R64, RecordQueue<SlotsLpf, kQueue>, RecordQueue<SlotsF32, kQueue>>>;
@@ -284,7 +407,9 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
         if (has) {
             double gy[3], acc[3], mag[3];
             Queue::unpack(cur, gy, acc, mag);
-            if (applied == 0)
+            bool first = applied == 0;
+            if constexpr (RESUME) first = first && fresh;
+            if (first)
                 ekf_record_step<kLoopForm>(x, state_norm2(x), P, Wr, kc, gy, dt, false, acc, mag, reload);
             else  // LAZY
                 ekf_record_step<kLoopForm, true>(x, 1.0, P, Wr, kc, gy, dt, false, acc, mag, reload);
@@ -344,6 +469,7 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
             if ((k + 1) % kFlush == 0) flush();
         },
         steps);
+    if constexpr (RESUME) LiveState<EV64>::store(state, batch, b, fe, x, P, applied0 + applied);
     counts[b] = applied;
     if (applied == 0) return;  // no record: the state is left as it was (as pekf_run_dev with counts)
     if constexpr (kLate) {
@@ -379,7 +505,7 @@ int launch_k_live(int64_t batch, int64_t n_events, const void *ev_planes, const 
     const dim3 grid(grid_for(batch, kRunBlock)), block(kRunBlock);
     auto launch = [&](auto kernel, const auto *ev) {
         hipLaunchKernelGGL(kernel, grid, block, 0, stream, batch, n_events, ev, init, t_init, alpha, q, r, X, P, counts,
-                           refs, traj, traj_dt, traj_rows);
+                           refs, traj, traj_dt, traj_rows, nullptr, 0);
     };
     if (flags & PEKF_EV_F64_EVENTS)  // the one FP64-event variant
         launch(k_live<false, false, true, TRAJ>, static_cast<const double4 *>(ev_planes));
@@ -391,6 +517,32 @@ int launch_k_live(int64_t batch, int64_t n_events, const void *ev_planes, const 
             (flags & PEKF_EV_TIME_EVENTS) != 0, (flags & PEKF_EV_F32_RECORDS) == 0);
     return launched("k_live");
 }
+// The argument checks every pekf_live_* entry shares, in two halves: sizes, flags and the trajectory arguments
+// (before the batch == 0 return), then the launch's limits and pointers (after it).
+static inline int check_live_flags(int64_t batch, int64_t n_events, uint32_t flags, const double *traj,
+                                   const double *traj_dt, int64_t traj_rows) {
+    PEKF_CHECK_ARG(batch >= 0 && n_events >= 0, "negative size");
+    PEKF_CHECK_ARG((flags & ~(PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS | PEKF_EV_F64_EVENTS)) == 0, "unknown flags");
+    const bool ev64 = (flags & PEKF_EV_F64_EVENTS) != 0;
+    PEKF_CHECK_ARG(!ev64 || (flags & (PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS)) == 0,
+                   "PEKF_EV_F64_EVENTS takes no other flag (FP64 events carry their times; their records are FP64)");
+    PEKF_CHECK_ARG(traj_rows >= 0 && traj_rows < ((int64_t)1 << 31), "traj_rows must be >= 0 and < 2^31");
+    PEKF_CHECK_ARG(traj_rows == 0 || (traj && (uintptr_t)traj % 16 == 0),
+                   "traj must be a 16-byte aligned pointer when traj_rows > 0");
+    PEKF_CHECK_ARG(traj_rows == 0 || (uintptr_t)traj_dt % 8 == 0, "misaligned traj_dt");
+    return PEKF_OK;
+}
+static inline int check_live_launch(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                                    const int64_t *t_init, const double *X, const double *P, double r,
+                                    const int32_t *counts, const double *refs) {
+    PEKF_CHECK_ARG(batch < ((int64_t)1 << 28), "batch must be < 2^28 filters per launch");
+    PEKF_CHECK_ARG(n_events < ((int64_t)1 << 30), "n_events must be < 2^30 per launch");
+    PEKF_CHECK_ARG(ev_planes && init && t_init && X && P && counts && refs, "null pointer");
+    PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
+    PEKF_CHECK_ARG(r > 0.0, "r must be > 0 (S = P- + rI must be SPD)");
+    return PEKF_OK;
+}
+
 // launch_k_live<true> (pekf_live_traj.hip)
 int launch_live_traj(int64_t batch, int64_t n_events, const void *ev_planes, const double *init, const int64_t *t_init,
                      double alpha, double *X, double *P, double q, double r, int32_t *counts, double *refs,

@@ -861,6 +861,152 @@ class BatchedEKF:
         return out + (tj.result(ev["t_init"]),) if tj.wanted else out
 
 
+def chunk_trajectory_rows(trajectory, n_events):
+    """trajectory_rows for one chunk of a LiveSession: True is (n_events + 2) // 3 rows, since a chunk's first
+    record may need one event only (its gyro and the other sample came in earlier chunks), every later one three."""
+    return (int(n_events) + 2) // 3 if trajectory is True else trajectory_rows(trajectory, n_events)
+
+
+class LiveSession:
+    """A live session fed in chunks (pekf_live_resume_dev): the phones' phase-3 events as they arrive, a launch
+    per chunk, the front-end's and the filter's state carried between them on the device.  However the events are
+    cut into chunks, X, P, refs, the summed counts and the concatenated trajectory rows have the bits of
+    BatchedEKF.run_events on all of them at once.
+
+    filters: a BatchedEKF (FP64, AoS) -- its X / P start the session and receive, after every chunk, the X_k / P of
+    the filters that applied a record in it; while the session runs they are outputs only (the session state
+    holds the filter).  init_acc / init_mag (K, 3) host arrays of the raw phase-2 means, or init_acc a DeviceBuffer
+    of phase 2's init (K, 6) and init_mag None (_launch_phase2's); t_init (K,) int64 host array or DeviceBuffer.
+    events: "f32" or "f64", fixed for the session (records are FP64 either way)."""
+
+    def __init__(self, filters, init_acc, init_mag, t_init, alpha=0.1, events="f32"):
+        if events not in EVENT_FORMS:
+            raise ValueError("events must be 'f32' or 'f64'")
+        if filters.layout != "aos" or filters.flags & RUN_MIXED_PRECISION:
+            raise ValueError("the fused front-end + filter kernel runs the FP64 filter on AoS state")
+        K = filters.batch
+        self.filters, self.batch, self.alpha, self.events = filters, K, float(alpha), events
+        self._form = EV_F64_EVENTS if events == "f64" else 0
+        if isinstance(init_acc, DeviceBuffer):
+            self._init = init_acc
+        else:
+            init = np.concatenate([np.asarray(init_acc, np.float64).reshape(K, 3),
+                                   np.asarray(init_mag, np.float64).reshape(K, 3)], axis=1)
+            self._init = DeviceBuffer(48 * K).upload(init)
+        if isinstance(t_init, DeviceBuffer):
+            self._t_init, t_host = t_init, t_init.download((K,), np.int64)
+        else:
+            t_host = np.ascontiguousarray(t_init, np.int64).reshape(K).copy()
+            self._t_init = DeviceBuffer(8 * K).upload(t_host)
+        self._alloc()
+        self._book = dict(started=False, t_init=t_host, last_times=t_host.copy(), dt_sum=np.zeros(K),
+                          total_counts=np.zeros(K, np.int64))
+
+    def _alloc(self):
+        K = self.batch
+        nbytes = int(lib.pekf_live_state_bytes(K, self._form))
+        if nbytes < 0:
+            raise ValueError("no session state for these flags")
+        self._state, self._cnt, self._refs = DeviceBuffer(nbytes), DeviceBuffer(4 * K), DeviceBuffer(48 * K)
+
+    @property
+    def total_counts(self):
+        """(K,) int64: the records each filter has applied since the session began"""
+        return self._book["total_counts"].copy()
+
+    @property
+    def refs(self):
+        """(K, 6) the filters' acc0 / mag0 (written by every launch; before the first, from a zero-event one)"""
+        if not self._book["started"]:
+            self.feed_planes(self._state, 0)
+        return self._refs.download((self.batch, 6), np.float64)
+
+    def pack_chunk(self, ev):
+        """A chunk's rows (types / values / times, optionally values64) -> (host planes, PEKF_EV_* flags) in the
+        session's event form.  f32: synth.pack_events with the chunk's first gap taken from the previous chunk's
+        last times row (t_init before the first), which the session keeps; null padding lands mid-stream."""
+        times = np.asarray(ev["times"], np.int64)
+        chunk = dict(ev, t_init=self._book["last_times"])
+        if self.events == "f64":
+            planes, flags = synth.pack_events64(chunk, server_event_values(chunk)), EV_F64_EVENTS
+        else:
+            planes = synth.pack_events(chunk)
+            flags = EV_TIME_EVENTS if synth.has_time_events(planes) else 0
+        if len(times):
+            self._book["last_times"] = times[-1].copy()
+        return planes, flags
+
+    def feed(self, ev, trajectory=False):
+        """The next rows of every filter's stream: a synth.generate_events-style dict of types (E, K), values
+        (E, K, 3), times (E, K) and optionally values64 (init_* / t_init entries are ignored).  Returns counts
+        (K,) int32, the records applied in this chunk, or with trajectory (True or a row cap) (counts, dict of
+        trajectory / record_dt_ns / record_times_ns) as run_events does, rows counted within the chunk."""
+        planes, flags = self.pack_chunk(ev)
+        buf = DeviceBuffer(planes.nbytes).upload(planes)
+        return self.feed_planes(buf, planes.shape[0], flags, trajectory)
+
+    def feed_planes(self, planes, n_events, flags=0, trajectory=False, offset=0):
+        """n_events packed rows ([n_events][K] float4, or double4 for an FP64-event session) of the DeviceBuffer
+        `planes`, starting `offset` bytes into it: row ranges of one resident plane are fed without copies.
+        flags: EV_TIME_EVENTS if these rows hold time events (it may differ from chunk to chunk)."""
+        K, book = self.batch, self._book
+        n_events, flags = int(n_events), int(flags) | self._form
+        row = K * (32 if self._form else 16)
+        if offset < 0 or offset % 16 or (n_events > 0 and offset + n_events * row > planes.nbytes):
+            raise ValueError("offset / n_events outside the planes buffer (or offset not a multiple of 16)")
+        tj = _Trajectory(chunk_trajectory_rows(trajectory, n_events) if trajectory is True else trajectory, n_events, K)
+        f = self.filters
+        check(lib.pekf_live_resume_dev(K, n_events, planes.ptr + offset, self._init.ptr, self._t_init.ptr, self.alpha,
+                                       f.X.ptr, f.P.ptr, f.q, f.r, self._cnt.ptr, self._refs.ptr, flags,
+                                       self._state.ptr, int(book["started"]), tj.traj.ptr if tj.rows else None,
+                                       tj.dt.ptr if tj.rows else None, tj.rows, None, None))
+        check(lib.pekf_device_sync())
+        book["started"] = True
+        counts = self._cnt.download((K,), np.int32)
+        book["total_counts"] += counts
+        if not tj.wanted:
+            book["dt_sum"] = np.where(counts > 0, np.nan, book["dt_sum"])   # these records' dts were not asked for
+            return counts
+        return counts, self._chunk_result(tj.result(np.zeros(K)), counts)
+
+    def _chunk_result(self, out, counts):
+        """The chunk's trajectory dict with record_times_ns continuing from the session's running record time: per
+        filter t_init + the running sum of every dt so far, summed in the order one launch's cumsum would.  A
+        filter whose earlier records' dts were not all downloaded (a chunk fed without a trajectory, or with a
+        row cap below its count) has NaN times from then on."""
+        book, dt = self._book, out["record_dt_ns"]
+        run = np.cumsum(np.concatenate([book["dt_sum"][None, :], dt], axis=0), axis=0)
+        out["record_times_ns"] = book["t_init"].astype(np.float64)[None, :] + run[1:]
+        seen = np.minimum(counts, len(dt))
+        last = run[seen, np.arange(self.batch)]
+        book["dt_sum"] = np.where(counts > len(dt), np.nan, last)
+        return out
+
+    def snapshot(self):
+        """The session as host data: dict(state (bytes of the device state as a uint8 array), X, P, refs and the
+        host-side bookkeeping).  LiveSession.restore continues from it on another BatchedEKF or device."""
+        K, book = self.batch, self._book
+        X, P = self.filters.get_state()
+        return dict(batch=K, events=self.events, alpha=self.alpha, q=self.filters.q, r=self.filters.r,
+                    state=self._state.download((self._state.nbytes,), np.uint8), X=X, P=P,
+                    init=self._init.download((K, 6), np.float64), refs=self._refs.download((K, 6), np.float64),
+                    book={k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in book.items()})
+
+    @classmethod
+    def restore(cls, filters, snapshot):
+        """A session that continues `snapshot` on `filters` (same batch, q and r; set the device first to move a
+        shard): its X / P are set to the snapshot's, the state is uploaded as it was."""
+        s = snapshot
+        if filters.batch != s["batch"] or (filters.q, filters.r) != (s["q"], s["r"]):
+            raise ValueError("restore needs a BatchedEKF of the snapshot's batch, q and r")
+        self = cls(filters, s["init"][:, :3], s["init"][:, 3:], s["book"]["t_init"], s["alpha"], s["events"])
+        filters.set_state(s["X"], s["P"])
+        self._state.upload(s["state"])
+        self._refs.upload(s["refs"])
+        self._book = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in s["book"].items()}
+        return self
+
+
 class FilterHandle:
     """B KalmanFilter objects behind one native handle (pekf_filter_*).
 

@@ -6,6 +6,8 @@
   frontend_then_filter   the filter over those records (pekf_run_dev with counts): the split pipeline
   live          pekf_live_dev: the same events -> filter in one launch (no record window); 16 B read per
                 event + the state once (PEKF_AUX_ONLY=live stops after it, =side after wahba_stream)
+  live_resume   PEKF_AUX_ONLY=live_resume, that case alone: pekf_live_resume_dev, the same session fed in 1, 8, 64
+                and 342 chunks beside the one launch, f32 and FP64 events (profiles/r15/live_resume/)
   gyro_chain    pekf_gyro_chain_dev (§8f-3): 16 B read per filter-record
   wahba_stream  pekf_wahba_stream_dev (§8f-3): 24 B read + 32 B written per filter-record
   predict_dev / correct_dev   per-call operators at n = 1M items (device pointers)
@@ -151,10 +153,85 @@ def percall_dev(s):
     return res
 
 
+def live_resume(s, K0=16384, E=1024, tile=64):
+    """A live session fed in chunks (pekf_live_resume_dev) beside the one launch (pekf_live_ext_dev), 1,048,576
+    filters x 1,024 events, FP64 records, for f32 and FP64 events: (a) the one launch, (b) the session in one
+    chunk -- a same-box A B B A of the two -- then 8 chunks of 128, 64 of 16 and 341 of 3 plus one of 1.  Each
+    case's time beside what its bytes predict: the state read and written per filter and launch at the HBM
+    fraction pekf_state_layout_dev (k_state_layout, a pure state copy) reaches on the same box."""
+    ev = bench_events(K0, E)
+    K = K0 * tile
+    init = np.tile(np.concatenate([ev["init_acc"], ev["init_mag"]], axis=1), (tile, 1))
+    ib = engine.DeviceBuffer(init.nbytes).upload(init)
+    tb = engine.DeviceBuffer(8 * K).upload(np.tile(ev["t_init"], tile).astype(np.int64))
+    f = engine.BatchedEKF(K)
+    cnt, refs = engine.DeviceBuffer(4 * K), engine.DeviceBuffer(48 * K)
+    # the yardstick of a state-sized copy: AoS -> SoA of X, P (160 B read, 112 B written per filter)
+    xs, ps = engine.DeviceBuffer(32 * K), engine.DeviceBuffer(80 * K)
+    ms = timed(lambda: check(lib.pekf_state_layout_dev(K, f.X.ptr, f.P.ptr, xs.ptr, ps.ptr, 1, s)), s, reps=9)
+    frac = K * 272 / (ms * 1e-3) / 1e9 / HBM
+    res = {"filters": K, "events_per_filter": E, "state_layout": {"kernel_ms": ms, "bytes": K * 272, "hbm_frac": frac}}
+    log("k_state_layout: %.3f ms, %.2f of HBM" % (ms, frac))
+    del xs, ps
+    cuts = {"b_1x1024": [E], "c_8x128": [128] * 8, "d_64x16": [16] * 64, "e_341x3+1": [3] * 341 + [1]}
+    for form, flags, row in (("f32", 0, 16), ("f64", engine.EV_F64_EVENTS, 32)):
+        src = synth.pack_events(ev) if form == "f32" else synth.pack_events64(ev, engine.server_event_values(ev))
+        assert src.shape[0] == E and not (form == "f32" and synth.has_time_events(src))
+        evb = engine.DeviceBuffer(E * K * row)
+        for e0 in range(0, E, 64):   # tiled and uploaded 64 rows at a time
+            blk = np.ascontiguousarray(np.tile(src[e0:e0 + 64], (1, tile, 1)))
+            check(lib.pekf_memcpy_h2d(evb.ptr + e0 * K * row, blk.ctypes.data, blk.nbytes, None))
+        del src, blk
+        sb = int(lib.pekf_live_state_bytes(K, flags))
+        state = engine.DeviceBuffer(sb)
+
+        def one_launch():
+            check(lib.pekf_live_ext_dev(K, E, evb.ptr, ib.ptr, tb.ptr, 0.1, f.X.ptr, f.P.ptr, f.q, f.r, cnt.ptr,
+                                        refs.ptr, flags, None, s))
+
+        def session(sizes):
+            def run():
+                e0 = 0
+                for i, n in enumerate(sizes):
+                    check(lib.pekf_live_resume_dev(K, n, evb.ptr + e0 * K * row, ib.ptr, tb.ptr, 0.1, f.X.ptr, f.P.ptr,
+                                                   f.q, f.r, cnt.ptr, refs.ptr, flags, state.ptr, int(i > 0), None,
+                                                   None, 0, None, s))
+                    e0 += n
+            return run
+        out = {"state_bytes_per_filter": sb // K}
+        abba = []
+        for name, fn in (("a", one_launch), ("b", session(cuts["b_1x1024"])), ("b", session(cuts["b_1x1024"])),
+                         ("a", one_launch)):
+            f.reset(s)
+            abba.append((name, timed(fn, s)))
+        out["abba_ms"] = abba
+        a_ms = float(np.mean([m for n, m in abba if n == "a"]))
+        out["a_one_launch_ms"] = a_ms
+        for name, sizes in cuts.items():
+            f.reset(s)
+            ms = timed(session(sizes), s)
+            # the state written by every launch and read by every launch but the first
+            byts = sb * (2 * len(sizes) - 1)
+            pred = byts / (frac * HBM * 1e9) * 1e3
+            out[name] = {"launches": len(sizes), "total_ms": ms, "ms_per_chunk": ms / len(sizes),
+                         "extra_ms": ms - a_ms, "state_bytes": byts, "predicted_extra_ms": pred,
+                         "unexplained_ms": ms - a_ms - pred,
+                         "unexplained_us_per_launch": (ms - a_ms - pred) / len(sizes) * 1e3}
+            log("%s events, %s: %.2f ms (%.3f per chunk), extra %.2f, predicted %.2f" %
+                (form, name, ms, ms / len(sizes), ms - a_ms, pred))
+        res[form] = out
+        del evb, state
+    res["device"] = engine.device_name(0)
+    return res
+
+
 def main():
     st = engine.Stream()
     s = st.handle
     res = {}
+    if os.environ.get("PEKF_AUX_ONLY") == "live_resume":
+        print(json.dumps({"live_resume": live_resume(s)}))
+        return
 
     # ---- front-end: 16K generated event streams tiled x64 -> 1,048,576 filters x 1,024 events
     K0, E, tile = 16384, 1024, 64

@@ -14,7 +14,9 @@ pekf_wire_dev.hip (COMMON alone).
 Each __global__ kernel of namespace pekf in old.s (the listing's .amdhsa_kernel names: k_reset, k_live<TE, R64,
 EV64, TRAJ>, k_run<Rec, ...>, k_op<OpWahba<1>>, whatever its template arguments) is compared with that of new.s:
 instructions and block labels, comments and assembler directives dropped, the kernel's own name and its number in
-the .LBB labels normalised.  A kernel is known by its name and template arguments, not by its parameter list.
+the .LBB labels normalised.  A kernel is known by its name and template arguments, not by its parameter list; one
+whose template gained trailing parameters that default to false (k_live<.., TRAJ> -> k_live<.., TRAJ, RESUME = 0>)
+is compared under its old label.
 Prints a line per kernel (lines, identical or the unified diff) and exits 1 on any difference, or on a kernel
 that only one of the listings has."""
 import difflib
@@ -100,8 +102,24 @@ def kernels(path):
     return out
 
 
+def _grown(label, new):
+    """The label in `new` of a kernel whose template gained trailing parameters that default to false
+    (k_live<1, 1, 0, 0> -> k_live<1, 1, 0, 0, 0>: the same kernel, as k_live<TE, R64, EV64> was k_live<.., TRAJ = 0>)"""
+    if not label.endswith(">"):
+        return None
+    for n in (1, 2, 3):
+        grown = label[:-1] + ", 0" * n + ">"
+        if grown in new:
+            return grown
+    return None
+
+
 def main(old_path, new_path):
     old, new = kernels(old_path), kernels(new_path)
+    for label in [k for k in old if k not in new]:
+        grown = _grown(label, new)
+        if grown:
+            new[label] = new.pop(grown)
     bad = 0
     for label in sorted(set(old) | set(new)):
         if label not in old or label not in new:
