@@ -370,6 +370,25 @@ int pekf_live_resume_dev(int64_t batch, int64_t n_events, const void *ev_planes,
  * `int pekf_...(` at the start of a line like every other entry's (tests/test_capi.py lists the ABI by that). */
 long long
 int pekf_live_state_bytes(int64_t batch, uint32_t flags);
+/* pekf_live_resume_dev for phones that do not move in lock-step: no `resume` word for the launch -- each filter
+ * joins the session by itself.  `state` (pekf_live_state_bytes(batch, PEKF_EV_F64_EVENTS) bytes) is zeroed by the
+ * caller before the first call; a mark in it says which filters have joined.  Per filter and call:
+ *   not joined: it starts fresh exactly as resume == 0 does, from THIS call's init / t_init and from X / P;
+ *   joined: it continues from the state exactly as resume != 0 does (X / P and t_init are not used for it).
+ * A filter joins at the end of a call in which it was ready (finite init) and its column held at least one
+ * message (an event that is not the no-message event).  Until then nothing of it is kept: no-message rows move no
+ * state, so its fresh start in the call that holds its first message is the one call over all rows.  The phase-3
+ * messages of a filter that is not ready are dropped, and it stays unjoined.  So init / t_init may change from
+ * call to call (pekf_frontend_init_resume_dev's outputs of the same chunk) until a filter joins; from then on its
+ * init must stay, which phase 2 guarantees (a ready phone's means never change).
+ *   FP64 events only: flags must be PEKF_EV_F64_EVENTS, anything else is PEKF_ERR_INVALID.  They carry absolute
+ * times; in the f32 planes a phone's first phase-3 gap is relative to its last phase-2 message and padding moves
+ * the clock, which a filter that keeps nothing until it joins would lose.  Every other check, and n_events == 0,
+ * as pekf_live_resume_dev with resume == 0 (a launch that writes refs and counts = 0). */
+int pekf_live_join_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                       const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
+                       int32_t *counts, double *refs, uint32_t flags, void *state, double *traj, double *traj_dt,
+                       int64_t traj_rows, int *dev_error, void *stream);
 
 /* Phase 2 of the server's Parser (KFS/Parser.cpp:36-58,84-140; KFS/InitialValues.cpp) on the device: per
  * filter, the mean and sample variance of the first n_avg (the server: 100) samples of each sensor type,
@@ -389,6 +408,28 @@ int pekf_frontend_init_dev(int64_t batch, int64_t n_events, const void *ev_plane
 int pekf_frontend_init_ext_dev(int64_t batch, int64_t n_events, const void *ev_planes, const int64_t *t_start,
                                int n_avg, double *init, int64_t *t_init, double *stats, int32_t *ready,
                                uint32_t flags, void *stream);
+/* Phase 2 fed in chunks: pekf_frontend_init_ext_dev's means on the next n_events rows of the same phones' phase-2
+ * plane.  resume == 0 starts a session from t_start as the one call does; resume != 0 continues it from `state`
+ * (t_start is then not read and may be NULL).  What carries over, in `state`: per phone the three running FP64
+ * sums, the three sample counts, the three "initialised" flags, the "filter built" flag and the two clocks.
+ *   init, t_init and ready are written by EVERY call and are what pekf_frontend_init_ext_dev with stats = NULL
+ * writes for all the rows fed so far, bit for bit, however they were cut into calls: a phone that is not ready
+ * has NaN means; a ready phone's means never change again (the sums stop once all three sensors are
+ * initialised), only its t_init moves, to each later message's time.
+ *   NO VARIANCES: there is no stats argument.  The reference's variance is a second pass over the first n_avg
+ * samples once the mean is known (KFS/InitialValues.cpp), and a chunked feed no longer has them; a one-pass
+ * formula would not give the reference's bits.  Use pekf_frontend_init_ext_dev on the whole plane for them.
+ *   state: a device buffer of pekf_frontend_init_state_bytes(batch, flags) bytes, 16-byte aligned, required; its
+ * layout is private and belongs to one batch, its bytes may be copied.  flags as pekf_frontend_init_ext_dev.
+ * The no-message / zero-step time events that pad a chunk move nothing.  n_events == 0 is legal: it changes
+ * nothing but the outputs (with resume == 0 it writes the fresh state). */
+int pekf_frontend_init_resume_dev(int64_t batch, int64_t n_events, const void *ev_planes, const int64_t *t_start,
+                                  int n_avg, double *init, int64_t *t_init, int32_t *ready, uint32_t flags,
+                                  void *state, int resume, void *stream);
+/* The bytes of a phase-2 session state for `batch` phones (host only); < 0: flags the call above refuses, or a
+ * negative batch.  64 bits, spelled as pekf_live_state_bytes is. */
+long long
+int pekf_frontend_init_state_bytes(int64_t batch, uint32_t flags);
 
 /* Phase 1 of the server's client session (KFS/Magnetometer_Calibration.cpp) on the device: per phone, the
  * magnetometer's hard-iron bias and soft-iron matrix W from its phase-1 messages.  Events as for

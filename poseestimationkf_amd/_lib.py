@@ -132,6 +132,10 @@ SIGNATURES = {
     "pekf_live_state_bytes": [_i64, _u32],
     "pekf_live_resume_dev": [_i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _dbl, _dbl, _vp, _vp, _u32, _vp, _int, _vp, _vp,
                              _i64, _vp, _vp],
+    "pekf_live_join_dev": [_i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _dbl, _dbl, _vp, _vp, _u32, _vp, _vp, _vp, _i64,
+                           _vp, _vp],
+    "pekf_frontend_init_resume_dev": [_i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _u32, _vp, _int, _vp],
+    "pekf_frontend_init_state_bytes": [_i64, _u32],
     "pekf_log_scan": [ctypes.c_char_p, ctypes.POINTER(_i64)],
     "pekf_log_read": [ctypes.c_char_p, _i64, _vp, _vp, _vp, _vp, _dp, _dp, _dp],
     "pekf_log_read_ext": [ctypes.c_char_p, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64), _dp, _dp, _dp],
@@ -153,7 +157,8 @@ SIGNATURES = {
     "pekf_gather_multi_dev": [_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i64, _vp, _int, ctypes.POINTER(_vp)],
     "pekf_allreduce_max_dev": [_vp, _vp, _i64, _vp],
 }
-_RESTYPE = {"pekf_abi_version": ctypes.c_int, "pekf_last_error": ctypes.c_char_p, "pekf_live_state_bytes": _i64}
+_RESTYPE = {"pekf_abi_version": ctypes.c_int, "pekf_last_error": ctypes.c_char_p, "pekf_live_state_bytes": _i64,
+            "pekf_frontend_init_state_bytes": _i64}
 
 
 def _load():

@@ -1,6 +1,7 @@
 // pekf_live.hpp -- k_live, the fused front-end + filter kernel, and its record queue (see pekf_live.hip,
 // which instantiates the kernels without trajectory output; pekf_live_traj.hip instantiates their TRAJ twins,
-// pekf_live_resume.hip the resumable kernels of a session fed in chunks).
+// pekf_live_resume.hip the resumable kernels of a session fed in chunks, pekf_live_join.hip those whose filters
+// join the session one by one).
 #pragma once
 #include "pekf_phase3.hpp"
 #include "pekf_step.hpp"
@@ -293,12 +294,17 @@ struct LiveState {
             fe.gyro = {s[3].x, s[3].y, s[3].z};
         }
     }
+    // the flag word's bit 5 (k_live<..., JOIN>): this lane has joined the session -- its state is to be resumed
+    static constexpr uint32_t kJoined = 32u;
+    static __device__ __forceinline__ bool joined(void *state, int64_t batch, int64_t b) {
+        return ((uint32_t)__double2loint(plane(state, batch, b, kDoubles / 2 - 1)->y) & kJoined) != 0;
+    }
     static __device__ __forceinline__ void store(void *state, int64_t batch, int64_t b, Fe &fe, double *x,
-                                                 Sym4T<double> &N, int32_t total) {
+                                                 Sym4T<double> &N, int32_t total, uint32_t mark = 0u) {
         double d[kDoubles];
         doubles<false>(fe, x, N, d);
         const uint32_t flags = (fe.acc0_mean ? 1u : 0u) | (fe.mag0_mean ? 2u : 0u) | (fe.gyro_set ? 4u : 0u) |
-                               (fe.acc1_set ? 8u : 0u) | (fe.mag1_set ? 16u : 0u);
+                               (fe.acc1_set ? 8u : 0u) | (fe.mag1_set ? 16u : 0u) | mark;
         d[kDoubles - 1] = __hiloint2double(total, (int)flags);
 #pragma unroll
         for (int p = 0; p < kDoubles / 2; ++p) *plane(state, batch, b, p) = make_double2(d[2 * p], d[2 * p + 1]);
@@ -332,7 +338,13 @@ struct LiveState {
 // record is applied by the call the single launch makes for it and any cutting of a session's events into
 // launches gives the single launch's bits.  X / P are written, and counts[b] and the trajectory rows count, per
 // launch.  The kernels without RESUME read neither argument.
-template <bool TE, bool R64, bool EV64 = false, bool TRAJ = false, bool RESUME = false>
+// JOIN (with RESUME, FP64 events: pekf_live_join_dev): each lane joins the session by itself.  Not `resume` but
+// the lane's own mark in its state's flag word (LiveState::kJoined; the caller zeroes the state before the first
+// launch) says whether it continues from the state or starts fresh as resume == 0 does, from this launch's init /
+// t_init and X / P.  A lane is marked, and its state stored, at the end of a launch in which it was ready and
+// its column held a message; until then nothing of it is kept -- null rows move no state, so the fresh start at
+// the launch with its first message is the one launch that walked the null rows before it.
+template <bool TE, bool R64, bool EV64 = false, bool TRAJ = false, bool RESUME = false, bool JOIN = false>
 __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 ? PEKF_LIVE_EV64_WAVES : 2))) void k_live(
     int64_t batch, int64_t n_events, const std::conditional_t<EV64, double4, float4> *__restrict__ ev,
     const double *__restrict__ init, const int64_t *__restrict__ t_init, double alpha, double qs, double rs,
@@ -349,6 +361,7 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     // SlotsLpf keeps ONE escaped dt per lane (esc_dt) and want_step drains it before the next block,
     // which is safe only while a block completes at most one record per lane
     static_assert(!R64 || kPush == 1, "SlotsLpf's single escaped-dt register needs one record per lane per block");
+    static_assert(!JOIN || (RESUME && EV64), "lanes join a resumable session of FP64 events (absolute times)");
     const int64_t b = (int64_t)blockIdx.x * kRunBlock + threadIdx.x;
     if (b >= batch) return;
 
@@ -367,6 +380,7 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     make_frame<true>(rf, rf + 3, Wf);
     double x[4];
     Sym4T<double> P;
+    if constexpr (JOIN) resume = LiveState<EV64>::joined(state, batch, b);  // the lane's own word, not the launch's
     if constexpr (RESUME) {
         // resumed: the state holds the filter (what enter_ref_basis rotates below is then replaced)
         if (resume) {
@@ -394,6 +408,7 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     Queue queue;
     queue.bind(q_lds);
     int32_t applied = 0;
+    bool seen = false;  // JOIN: the lane's column held a message in this launch
     // One filter step for every lane with a queued record: its oldest, Prediction + Correction with
     // the multi-record kernel's arithmetic (the first record of the launch from the loaded |X|^2,
     // every later one lazy; front-end records always carry a magnetometer sample).
@@ -466,10 +481,17 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
                 fe.event64(v4);
             else
                 fe.template event<TE>(v4);
+            if constexpr (JOIN) seen = seen || is_message(v4);
             if ((k + 1) % kFlush == 0) flush();
         },
         steps);
-    if constexpr (RESUME) LiveState<EV64>::store(state, batch, b, fe, x, P, applied0 + applied);
+    if constexpr (JOIN) {
+        // joined before, or joining now; a lane that has not joined leaves its (zero) state as it is
+        if (resume || (ready && seen))
+            LiveState<EV64>::store(state, batch, b, fe, x, P, applied0 + applied, LiveState<EV64>::kJoined);
+    } else if constexpr (RESUME) {
+        LiveState<EV64>::store(state, batch, b, fe, x, P, applied0 + applied);
+    }
     counts[b] = applied;
     if (applied == 0) return;  // no record: the state is left as it was (as pekf_run_dev with counts)
     if constexpr (kLate) {

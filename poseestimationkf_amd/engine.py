@@ -1007,6 +1007,167 @@ class LiveSession:
         return self
 
 
+class PhoneSession:
+    """Live sessions from the phones' first message, fed as a server gets them: every chunk carries the next rows of
+    the phase-2 plane and of the phase-3 plane (or the clients' wire frames), and costs two launches -- phase 2
+    resumed (pekf_frontend_init_resume_dev), then phase 3 + the filter (pekf_live_join_dev) on phase 2's outputs
+    in device memory.  Phones do not move in lock-step: in one chunk some still average, some get ready, some
+    already filter; each filter joins the fused session by itself, in the chunk that holds its first phase-3
+    message once it is ready.
+
+    For every phone whose phase-2 messages all come before its phase-3 messages (the client's own order), any
+    cutting of the rows into chunks gives run_session(phase2, phase3, filters, events="f64") -- for frames
+    run_wire_session(frames, filters) -- bit for bit: X, P, refs, ready, the summed counts and the concatenated
+    trajectory / record_dt_ns / record_times_ns rows.  Outside that order: the phase-3 messages of a phone that
+    is not ready are dropped, and phase-2 messages after a phone joined move only a t_init nobody reads.
+
+    Sessions run on FP64 events (absolute times; pekf_live_join_dev takes nothing else).  filters: a BatchedEKF
+    (FP64, AoS), as LiveSession's.  t_start (K,) int64: phase 2's start time (None: 0), with FP64 events only
+    the t_init of a phone that never gets ready."""
+
+    def __init__(self, filters, n_avg=100, alpha=0.1, t_start=None):
+        if filters.layout != "aos" or filters.flags & RUN_MIXED_PRECISION:
+            raise ValueError("the fused front-end + filter kernel runs the FP64 filter on AoS state")
+        K = filters.batch
+        self.filters, self.batch, self.n_avg, self.alpha = filters, K, int(n_avg), float(alpha)
+        t0 = np.zeros(K, np.int64) if t_start is None else np.ascontiguousarray(t_start, np.int64).reshape(K)
+        self._alloc()
+        self._t_start.upload(t0)
+        check(lib.pekf_memset(self._state.ptr, 0, self._state.nbytes, None))   # no filter has joined
+        check(lib.pekf_device_sync())
+        self._book = dict(started=False, t_init=np.zeros(K, np.int64), dt_sum=np.zeros(K),
+                          total_counts=np.zeros(K, np.int64))
+
+    def _alloc(self):
+        K = self.batch
+        n2, n3 = int(lib.pekf_frontend_init_state_bytes(K, EV_F64_EVENTS)), int(lib.pekf_live_state_bytes(K, EV_F64_EVENTS))
+        if n2 < 0 or n3 < 0:
+            raise ValueError("no session state for FP64 events")
+        self._p2state, self._state = DeviceBuffer(n2), DeviceBuffer(n3)
+        self._t_start, self._init, self._t_init = DeviceBuffer(8 * K), DeviceBuffer(48 * K), DeviceBuffer(8 * K)
+        self._ready, self._cnt, self._refs = DeviceBuffer(4 * K), DeviceBuffer(4 * K), DeviceBuffer(48 * K)
+
+    total_counts = LiveSession.total_counts
+    _chunk_result = LiveSession._chunk_result
+
+    @property
+    def refs(self):
+        """(K, 6) the filters' acc0 / mag0 as of the last chunk (NaN for a phone that is not ready)"""
+        if not self._book["started"]:
+            self._launch(None, 0, None, 0, False, None)
+        return self._refs.download((self.batch, 6), np.float64)
+
+    def _pack(self, ev, name):
+        """A chunk's rows of one phase -> (DeviceBuffer or None, rows)"""
+        if ev is None:
+            return None, 0
+        shape = np.asarray(ev["types"]).shape
+        if len(shape) != 2 or shape[1] != self.batch:
+            raise ValueError("%s is of %s phones, the session of %d" % (name, shape[1:], self.batch))
+        if shape[0] == 0:
+            return None, 0
+        planes = synth.pack_events64(ev, server_event_values(ev))
+        return DeviceBuffer(planes.nbytes).upload(planes), shape[0]
+
+    def feed(self, phase2=None, phase3=None, trajectory=False, calibration=None):
+        """The next rows of the phase-2 plane and of the phase-3 plane: each a dict of types (E, K), values
+        (E, K, 3), times (E, K) and optionally values64, synth.EV_NONE where a phone has no message in a row;
+        either may be None or have no rows, and the two need not have the same number.  calibration:
+        calibrate_magnetometer's dict; both chunks are corrected on the device first (pekf_magcal_apply_dev: per
+        event, so it needs no state).  Returns (counts (K,) int32 records applied in this chunk, ready (K,) bool
+        phase 2's state after it), and with trajectory (True or a row cap) a third value, the dict of trajectory /
+        record_dt_ns / record_times_ns as LiveSession.feed's, rows counted within the chunk."""
+        b2, E2 = self._pack(phase2, "phase2")
+        b3, E3 = self._pack(phase3, "phase3")
+        return self._launch(b2.ptr if E2 else None, E2, b3.ptr if E3 else None, E3, trajectory, calibration)
+
+    def feed_planes(self, planes2, n2, planes3, n3, trajectory=False, calibration=None, offset2=0, offset3=0):
+        """Row ranges of resident FP64 event planes ([rows][K] double4 DeviceBuffers), without copies: n2 rows of
+        planes2 from byte offset2, n3 rows of planes3 from offset3 (offsets as LiveSession.feed_planes': inside the
+        buffer, multiples of 16).  A buffer whose row count is 0 may be None.  calibration corrects the rows in
+        place, so feed a row once."""
+        K = self.batch
+        ptrs = []
+        for planes, n, offset in ((planes2, int(n2), int(offset2)), (planes3, int(n3), int(offset3))):
+            if n < 0 or offset < 0 or offset % 16 or (n > 0 and (planes is None or offset + n * 32 * K > planes.nbytes)):
+                raise ValueError("offset / rows outside the planes buffer (or offset not a multiple of 16)")
+            ptrs.append(planes.ptr + offset if n else None)
+        return self._launch(ptrs[0], int(n2), ptrs[1], int(n3), trajectory, calibration)
+
+    def feed_frames(self, frames_chunk, calibration=None, trajectory=False):
+        """The next [F][K][100] wire frames of the phones (wire.frames): parsed with a row per frame
+        (wire_events(..., frame_rows=True): a frame's parse does not depend on earlier frames, and row f of each
+        plane is frame f's message of that phase), then fed as feed_planes.  calibration: a dict, as feed;
+        "frames" is refused -- phase 1 is not chunked, calibrate first (calibrate_magnetometer)."""
+        if isinstance(calibration, str):
+            raise ValueError("a chunked session takes calibrate_magnetometer's dict: phase 1 from the frames "
+                             "(calibration='frames') is not chunked")
+        F, Kf = _frames_shape(frames_chunk)
+        if Kf != self.batch:
+            raise ValueError("the frames are of %d phones, the session of %d" % (Kf, self.batch))
+        if F == 0:
+            return self._launch(None, 0, None, 0, trajectory, calibration)
+        w = wire_events(frames_chunk, None, True)
+        return self.feed_planes(w["ev2"], w["E2"], w["ev3"], w["E3"], trajectory, calibration,
+                                offset3=32 * self.batch * w["ev3_from"])
+
+    def _launch(self, ev2, E2, ev3, E3, trajectory, calibration):
+        K, book, f = self.batch, self._book, self.filters
+        if calibration is not None:
+            if E2:
+                _apply_calibration(calibration, K, E2, ev2, EV_F64_EVENTS)
+            if E3:
+                _apply_calibration(calibration, K, E3, ev3, EV_F64_EVENTS)
+        check(lib.pekf_frontend_init_resume_dev(K, E2, ev2, self._t_start.ptr, self.n_avg, self._init.ptr,
+                                                self._t_init.ptr, self._ready.ptr, EV_F64_EVENTS, self._p2state.ptr,
+                                                int(book["started"]), None))
+        tj = _Trajectory(chunk_trajectory_rows(trajectory, E3) if trajectory is True else trajectory, E3, K)
+        # (no rows: any valid pointer, none is read)
+        check(lib.pekf_live_join_dev(K, E3, ev3 if E3 else self._state.ptr, self._init.ptr, self._t_init.ptr,
+                                     self.alpha, f.X.ptr, f.P.ptr, f.q, f.r, self._cnt.ptr, self._refs.ptr,
+                                     EV_F64_EVENTS, self._state.ptr, tj.traj.ptr if tj.rows else None,
+                                     tj.dt.ptr if tj.rows else None, tj.rows, None, None))
+        check(lib.pekf_device_sync())
+        book["started"] = True
+        counts = self._cnt.download((K,), np.int32)
+        ready = self._ready.download((K,), np.int32).astype(bool)
+        # a phone's record times start from the t_init of the chunk in which it applies its first record
+        first = (book["total_counts"] == 0) & (counts > 0)
+        if first.any():
+            book["t_init"] = np.where(first, self._t_init.download((K,), np.int64), book["t_init"])
+        book["total_counts"] += counts
+        if not tj.wanted:
+            book["dt_sum"] = np.where(counts > 0, np.nan, book["dt_sum"])   # these records' dts were not asked for
+            return counts, ready
+        return counts, ready, self._chunk_result(tj.result(np.zeros(K)), counts)
+
+    _BUFFERS = ("p2state", "state", "t_start", "init", "t_init", "ready", "refs")
+
+    def snapshot(self):
+        """The session as host data, as LiveSession.snapshot: the bytes of both device states (phase 2's and the
+        fused kernel's), phase 2's latest outputs, X, P, refs and the host-side bookkeeping."""
+        X, P = self.filters.get_state()
+        snap = dict(batch=self.batch, n_avg=self.n_avg, alpha=self.alpha, q=self.filters.q, r=self.filters.r, X=X, P=P,
+                    book={k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in self._book.items()})
+        for name in self._BUFFERS:
+            buf = getattr(self, "_" + name)
+            snap[name] = buf.download((buf.nbytes,), np.uint8)
+        return snap
+
+    @classmethod
+    def restore(cls, filters, snapshot):
+        """A session that continues `snapshot` on `filters` (same batch, q and r), as LiveSession.restore."""
+        s = snapshot
+        if filters.batch != s["batch"] or (filters.q, filters.r) != (s["q"], s["r"]):
+            raise ValueError("restore needs a BatchedEKF of the snapshot's batch, q and r")
+        self = cls(filters, s["n_avg"], s["alpha"])
+        filters.set_state(s["X"], s["P"])
+        for name in cls._BUFFERS:
+            getattr(self, "_" + name).upload(s[name])
+        self._book = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in s["book"].items()}
+        return self
+
+
 class FilterHandle:
     """B KalmanFilter objects behind one native handle (pekf_filter_*).
 

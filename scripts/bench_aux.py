@@ -8,6 +8,8 @@
                 event + the state once (PEKF_AUX_ONLY=live stops after it, =side after wahba_stream)
   live_resume   PEKF_AUX_ONLY=live_resume, that case alone: pekf_live_resume_dev, the same session fed in 1, 8, 64
                 and 342 chunks beside the one launch, f32 and FP64 events (profiles/r15/live_resume/)
+  phone_session PEKF_AUX_ONLY=phone_session, that case alone: pekf_frontend_init_resume_dev + pekf_live_join_dev per
+                chunk beside one-shot phase 2 + pekf_live_resume_dev, 1, 8 and 64 chunks (profiles/r16/live_start/)
   gyro_chain    pekf_gyro_chain_dev (§8f-3): 16 B read per filter-record
   wahba_stream  pekf_wahba_stream_dev (§8f-3): 24 B read + 32 B written per filter-record
   predict_dev / correct_dev   per-call operators at n = 1M items (device pointers)
@@ -225,12 +227,114 @@ def live_resume(s, K0=16384, E=1024, tile=64):
     return res
 
 
+def phone_session(s, K0=16384, E=1024, tile=64, n_avg=100):
+    """Sessions fed from the phones' first message (pekf_frontend_init_resume_dev + pekf_live_join_dev per chunk)
+    beside the route that needs phase 2 finished first (one pekf_frontend_init_ext_dev over the whole phase-2
+    plane, then pekf_live_resume_dev on the phase-3 plane in the same chunks): 1,048,576 phones x 1,024 rows of
+    FP64 events, phone k's first 600 + 8 (k % 8) rows in the phase-2 plane and the rest in the phase-3 plane
+    (no-message events elsewhere), fed in 1, 8 and 64 chunks; a same-box A B B A per chunking.  The new route
+    reads each phone's rows twice, once per plane, and zeroes the join state before every session (timed with
+    it).  Then the phase-2 chunk launch alone beside what its bytes predict at the HBM fraction
+    pekf_state_layout_dev (k_state_layout, a pure state copy) reaches on the same box."""
+    ev = bench_events(K0, E)
+    K, flags, row = K0 * tile, engine.EV_F64_EVENTS, 32
+    cut = 600 + 8 * (np.arange(K0) % 8)
+    in2 = np.arange(E)[:, None] < cut[None, :]
+    vals = engine.server_event_values(ev)
+    planes = []
+    for keep in (in2, ~in2):
+        src = synth.pack_events64(dict(ev, types=np.where(keep, ev["types"], synth.EV_NONE)), vals)
+        buf = engine.DeviceBuffer(E * K * row)
+        for e0 in range(0, E, 64):   # tiled and uploaded 64 rows at a time
+            blk = np.ascontiguousarray(np.tile(src[e0:e0 + 64], (1, tile, 1)))
+            check(lib.pekf_memcpy_h2d(buf.ptr + e0 * K * row, blk.ctypes.data, blk.nbytes, None))
+        planes.append(buf)
+        del src, blk
+    ev2, ev3 = planes
+    f = engine.BatchedEKF(K)
+    tsb = engine.DeviceBuffer(8 * K).upload(np.tile(ev["t_init"], tile).astype(np.int64))
+    ib, tb, rb = engine.DeviceBuffer(48 * K), engine.DeviceBuffer(8 * K), engine.DeviceBuffer(4 * K)
+    cnt, refs = engine.DeviceBuffer(4 * K), engine.DeviceBuffer(48 * K)
+    sb2, sb3 = int(lib.pekf_frontend_init_state_bytes(K, flags)), int(lib.pekf_live_state_bytes(K, flags))
+    st2, st3 = engine.DeviceBuffer(sb2), engine.DeviceBuffer(sb3)
+    xs, ps = engine.DeviceBuffer(32 * K), engine.DeviceBuffer(80 * K)
+    ms = timed(lambda: check(lib.pekf_state_layout_dev(K, f.X.ptr, f.P.ptr, xs.ptr, ps.ptr, 1, s)), s, reps=9)
+    frac = K * 272 / (ms * 1e-3) / 1e9 / HBM
+    res = {"phones": K, "rows": E, "n_avg": n_avg, "phase2_state_bytes_per_phone": sb2 // K,
+           "join_state_bytes_per_phone": sb3 // K,
+           "state_layout": {"kernel_ms": ms, "bytes": K * 272, "hbm_frac": frac}}
+    log("k_state_layout: %.3f ms, %.2f of HBM" % (ms, frac))
+    del xs, ps
+
+    def phase2_chunk(e0, n, resume):
+        check(lib.pekf_frontend_init_resume_dev(K, n, ev2.ptr + e0 * K * row, tsb.ptr, n_avg, ib.ptr, tb.ptr, rb.ptr,
+                                                flags, st2.ptr, resume, s))
+
+    def parent_route(sizes):
+        def run():
+            check(lib.pekf_frontend_init_ext_dev(K, E, ev2.ptr, tsb.ptr, n_avg, ib.ptr, tb.ptr, None, rb.ptr, flags, s))
+            e0 = 0
+            for i, n in enumerate(sizes):
+                check(lib.pekf_live_resume_dev(K, n, ev3.ptr + e0 * K * row, ib.ptr, tb.ptr, 0.1, f.X.ptr, f.P.ptr, f.q,
+                                               f.r, cnt.ptr, refs.ptr, flags, st3.ptr, int(i > 0), None, None, 0, None,
+                                               s))
+                e0 += n
+        return run
+
+    def new_route(sizes):
+        def run():
+            check(lib.pekf_memset(st3.ptr, 0, sb3, s))
+            e0 = 0
+            for i, n in enumerate(sizes):
+                phase2_chunk(e0, n, int(i > 0))
+                check(lib.pekf_live_join_dev(K, n, ev3.ptr + e0 * K * row, ib.ptr, tb.ptr, 0.1, f.X.ptr, f.P.ptr, f.q,
+                                             f.r, cnt.ptr, refs.ptr, flags, st3.ptr, None, None, 0, None, s))
+                e0 += n
+        return run
+
+    final = {}
+    for chunks in (1, 8, 64):
+        sizes = [E // chunks] * chunks
+        abba = []
+        for name, fn in (("a", parent_route(sizes)), ("b", new_route(sizes)), ("b", new_route(sizes)),
+                         ("a", parent_route(sizes))):
+            f.reset(s)
+            abba.append((name, timed(fn, s)))
+        a_ms, b_ms = (float(np.mean([m for n, m in abba if n == which])) for which in "ab")
+        # the same result either way: the last timed session ran on the state the repetitions before it left, so
+        # compare the filters of one fresh session of each route
+        for which, fn in (("a", parent_route(sizes)), ("b", new_route(sizes))):
+            f.reset(s)
+            fn()
+            check(lib.pekf_stream_sync(s))
+            final[which] = f.X.download((K, 4), np.float64)
+        n = E // chunks
+        # the phase-2 chunk launch alone (a middle chunk): n events, the state read and written, the outputs
+        p2_ms = timed(lambda: phase2_chunk((chunks // 2) * n, n, 1), s, reps=9)
+        p2_bytes = K * (n * row + 2 * (sb2 // K) + 48 + 8 + 4)
+        res["chunks_%d" % chunks] = {
+            "abba_ms": abba, "a_parent_route_ms": a_ms, "b_phone_session_ms": b_ms, "b_over_a": b_ms / a_ms,
+            "b_ms_per_chunk": b_ms / chunks, "a_ms_per_chunk": a_ms / chunks, "same_final_X": bool(
+                np.array_equal(final["a"], final["b"])),
+            "phase2_chunk": {"kernel_ms": p2_ms, "bytes": p2_bytes, "predicted_ms": p2_bytes / (frac * HBM * 1e9) * 1e3,
+                             "hbm_frac": p2_bytes / (p2_ms * 1e-3) / 1e9 / HBM}}
+        log("%d chunks: parent route %.2f ms, phone session %.2f ms (%.3f per chunk); phase-2 chunk %.3f ms, "
+            "predicted %.3f" % (chunks, a_ms, b_ms, b_ms / chunks, p2_ms, res["chunks_%d" % chunks]["phase2_chunk"][
+                "predicted_ms"]))
+    res["ready"] = int(rb.download((K,), np.int32).sum())
+    res["device"] = engine.device_name(0)
+    return res
+
+
 def main():
     st = engine.Stream()
     s = st.handle
     res = {}
     if os.environ.get("PEKF_AUX_ONLY") == "live_resume":
         print(json.dumps({"live_resume": live_resume(s)}))
+        return
+    if os.environ.get("PEKF_AUX_ONLY") == "phone_session":
+        print(json.dumps({"phone_session": phone_session(s)}))
         return
 
     # ---- front-end: 16K generated event streams tiled x64 -> 1,048,576 filters x 1,024 events
