@@ -694,7 +694,12 @@ PEKF_DEV void wahba_matrix_toward(const RW &W, const Reload &reload, const doubl
 // and q' ~ q_th (x) q_1.  A vector c of the measured plane (c . n = 0) is taken by q_1 = (A0, A1, A2, 0)
 // to A0 (c_x, c_y) + c_z (A2, -A1) times one positive factor, the same for a and m, which drops out of
 // the angle; with a', m' these in-plane coordinates, the 2x2 core of wahba_rotation is
-//   C = ka aW a'_x + km (b1W m'_x + b2W m'_y),   S = km (b2W m'_x - b1W m'_y) - ka aW a'_y.
+//   C = ka aW a'_x + km T1,   S = km T2 - ka aW a'_y,   T1 = b1W m'_x + b2W m'_y,   T2 = b2W m'_x - b1W m'_y.
+// The weights sum to one (km = 1 - ka, ExtendedKalmanFilter.py:71), so the core is the blend
+//   C = T1 + ka (aW a'_x - T1),   S = T2 - ka (aW a'_y + T2),
+// two FMAs each from T1, T2: 8 operations, where the weighted products kaw = ka aW, kb = km b1W,
+// kw = km b2W and the two sums took 9 and km one more.  The rounding differs from the weighted form's; its
+// error against an extended-precision yardstick is the same size (tests/test_wahba_folded_cpu.py).
 // Conditioning.  A half-angle form (1 + cos, sin) cancels near a half turn: its angle error is
 // (eps / 2) tan(phi / 2).  The attitude of a moving body takes every value, so on a real stream some
 // lane of a wave is always near a half turn of one of the arcs (a branch to another form there would be
@@ -710,22 +715,26 @@ PEKF_DEV void wahba_matrix_toward(const RW &W, const Reload &reload, const doubl
 // which no reciprocal is used (sqrt_fast).
 // The state-independent half (it depends on the record's samples only, not on the prediction z), for
 // ekf_record_step's HOIST schedule: q' unnormalised.  Inputs it does not serve, all sent to the matrix
-// chain by wahba_toward_from_product: km < 0 (|acc_z| > 1, the reflection case of wahba_sign); a zero
+// chain by wahba_toward_from_product: ka > 1 (km < 0, the reflection case of wahba_sign); a zero
 // sample or acc parallel to mag (n = 0, N = 0 * inf = NaN, so q' NaN); and rho2 = 0 with n_z < 0 (q' = 0,
 // so its scale is NaN), which needs a_z = m_z = 0, hence ka = 0: a rank-1 B exactly in the xy plane.
 template <int F = 1, class RW, std::enable_if_t<RW::kRefBasis, int> = 0>
-PEKF_DEV void wahba_product_ref(const RW &W, const double *a, const double *m, double ka, double km, double *q) {
+PEKF_DEV void wahba_product_ref(const RW &W, const double *a, const double *m, double ka, double *q) {
     const double nx = a[1] * m[2] - a[2] * m[1], ny = a[2] * m[0] - a[0] * m[2], nz = a[0] * m[1] - a[1] * m[0];
     const double rho2 = nx * nx + ny * ny;
     const double w = sqrt_fast<F>(rho2 + nz * nz) + fabs(nz);
     const bool f1 = nz >= 0.0;
-    // q_1 = (A0, A1, -B2, 0): the negation rides on the products below
-    const double A0 = f1 ? w : rho2, A1 = f1 ? ny : w * ny, B2 = f1 ? nx : w * nx;
+    // q_1 = (A0, A1, -B2, 0): the negation rides on the products below.  A1 and B2 select their factor,
+    // 1 or w, not the products: one selected double instead of two, the same values (x * 1.0 is exact)
+    const double mu = f1 ? 1.0 : w;
+    const double A0 = f1 ? w : rho2, A1 = mu * ny, B2 = mu * nx;
     const double ax = A0 * a[0] - B2 * a[2], ay = A0 * a[1] - A1 * a[2];                // a', m'
     const double mx = A0 * m[0] - B2 * m[2], my = A0 * m[1] - A1 * m[2];
-    const double kaw = ka * W.aW, kb = km * W.b1W, kw = km * W.b2W;
-    const double C = kaw * ax + kb * mx + kw * my;
-    const double S = kw * mx - kb * my - kaw * ay;
+    // (C, S) = ka (aW a'_x, -aW a'_y) + (1 - ka) (T1, T2), as T + ka (. - T): km = 1 - ka is not formed
+    const double T1 = W.b1W * mx + W.b2W * my;
+    const double T2 = W.b2W * mx - W.b1W * my;
+    const double C = fma(ka, fma(W.aW, ax, -T1), T1);
+    const double S = fma(-ka, fma(W.aW, ay, T2), T2);
     const double wt = sqrt_fast<F>(C * C + S * S) + fabs(C);
     const bool ft = C >= 0.0;
     const double c0 = ft ? wt : S, c3 = ft ? S : wt;                                    // q_th = (c0, 0, 0, c3)
@@ -738,30 +747,33 @@ PEKF_DEV void wahba_product_ref(const RW &W, const double *a, const double *m, d
 // The z-dependent half: q' scaled to unit length with the sign of q'.z, and the fallback to the matrix
 // chain where |q'.z| < |q'| / 4 (as nv < 1 of Q4 z: the measured attitude more than ~150 degrees from the
 // prediction), km < 0 or NaN (a degenerate frame).  None occurs on a tracked stream, so the fallback
-// costs a wave nothing unless one of its lanes needs it.
+// costs a wave nothing unless one of its lanes needs it.  km = 1 - ka >= 0 holds exactly when ka <= 1
+// (the subtraction's sign is exact, and a NaN fails both), so the test reads ka and km is not formed.
 // pin(): called before the fallback branch (ekf_record_step's PIN schedule, pekf_step.hpp).
 // reload(acc, mag): the record's samples again, for the fallback only.  The caller re-reads them (memory,
 // LDS) instead of holding six doubles in registers to the end of the chain.
 template <int F = 1, class RW, class Reload, class Pin = NoPin, std::enable_if_t<RW::kRefBasis, int> = 0>
-PEKF_DEV void wahba_toward_from_product(const RW &W, const double *q, double km, const double *z,
+PEKF_DEV void wahba_toward_from_product(const RW &W, const double *q, double ka, const double *z,
                                         double *v, double &sc, const Reload &reload, const Pin &pin = Pin()) {
     const double c = fma(q[0], z[0], fma(q[1], z[1], fma(q[2], z[2], q[3] * z[3])));
     const double nq = fma(q[0], q[0], fma(q[1], q[1], fma(q[2], q[2], q[3] * q[3])));
     sc = copysign(rsqrt<F>(nq), c);
     v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
     pin();
-    if (PEKF_TAKEN(!(c * sc >= 0.25) || !(km >= 0.0), false)) {  // (NaN too)
+    if (PEKF_TAKEN(!(c * sc >= 0.25) || !(ka <= 1.0), false)) {  // (NaN too)
         wahba_matrix_toward<F>(W, reload, z, v, sc);
     }
 }
 
-// Both halves in one piece (every schedule but HOIST)
+// Both halves in one piece (every schedule but HOIST).  km = 1 - ka is named so that one call serves
+// either basis (the Frame overload below reads it); this form does not, and the caller's subtraction
+// goes with it.
 template <int F = 1, class RW, class Reload, class Pin = NoPin, std::enable_if_t<RW::kRefBasis, int> = 0>
-PEKF_DEV void wahba_quat_toward(const RW &W, const double *acc, const double *mag, double ka, double km,
+PEKF_DEV void wahba_quat_toward(const RW &W, const double *acc, const double *mag, double ka, double /* km */,
                                 const double *z, double *v, double &sc, const Reload &reload, const Pin &pin = Pin()) {
     double q[4];
-    wahba_product_ref<F>(W, acc, mag, ka, km, q);
-    wahba_toward_from_product<F>(W, q, km, z, v, sc, reload, pin);
+    wahba_product_ref<F>(W, acc, mag, ka, q);
+    wahba_toward_from_product<F>(W, q, ka, z, v, sc, reload, pin);
 }
 
 // Y = v * sc in the world basis (the plain form of ekf_record_step) from the two frames: the matrix chain
@@ -1010,7 +1022,7 @@ PEKF_DEV void rk4_closed(const double *x, double n2, double dt_ns, const double 
                          double &kk, double &in) {
     const double h = dt_ns * kNsToS;
     const double xx = (h * h) * th2;
-    const double ca = 1.0 - 0.5 * xx + xx * xx * (1.0 / 24.0);
+    const double ca = fma(xx, fma(xx, 1.0 / 24.0, -0.5), 1.0);  // 1 - xx/2 + xx^2/24 by Horner
     const double cb = h * (1.0 - xx * (1.0 / 6.0));
     kk = ca * ca + (cb * cb) * th2;
     in = rsqrt<true>(kk * n2);
@@ -1029,7 +1041,7 @@ PEKF_DEV void rk4_closed_w(const double *x, double n2, double dt_ns, const doubl
                            double &kk, double &in) {
     const double h = dt_ns * kNsToS;
     const double xx = mul_half(h * h, th2x2);  // h^2 |h_w|^2
-    const double ca = 1.0 - 0.5 * xx + xx * xx * (1.0 / 24.0);
+    const double ca = fma(xx, fma(xx, 1.0 / 24.0, -0.5), 1.0);  // 1 - xx/2 + xx^2/24 by Horner
     const double cb = h * (1.0 - xx * (1.0 / 6.0));
     kk = fma(ca, ca, mul_half(cb, cb) * th2x2);
     in = rsqrt<2>(kk * n2);

@@ -397,7 +397,7 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4 &P, c
         const Sym4 Si = spd_inverse_schur<LOOP>(S2);
         const double ka = fabs(acc[2]);              // (:71)
         double qm[4];
-        wahba_product_ref<F>(Wf, acc, mag, ka, 1.0 - ka, qm);
+        wahba_product_ref<F>(Wf, acc, mag, ka, qm);
         asm volatile("" ::"v"(Si.a00), "v"(Si.a01), "v"(Si.a02), "v"(Si.a03), "v"(Si.a11), "v"(Si.a12),
                      "v"(Si.a13), "v"(Si.a22), "v"(Si.a23), "v"(Si.a33), "v"(qm[0]), "v"(qm[1]), "v"(qm[2]),
                      "v"(qm[3]));
@@ -405,7 +405,7 @@ __device__ __forceinline__ void ekf_record_step(double *x, double n2, Sym4 &P, c
             record_skip<LOOP>(x, z, P, S2, k);
         } else {
             double v[4], sc;
-            wahba_toward_from_product<F>(Wf, qm, 1.0 - ka, z, v, sc, reload);  // Wahba.py:8-47 + the flip of :73-75
+            wahba_toward_from_product<F>(Wf, qm, ka, z, v, sc, reload);  // Wahba.py:8-47 + the flip of :73-75
             record_correct<LOOP>(x, z, P, Si, v, sc, k);
         }
         return;
