@@ -9,18 +9,16 @@
 // reciprocal / rsqrt with a Newton step instead of IEEE divisions: ~1e-15 relative), records
 // rounded to f32 like every record of the stream.  Event plane: EV float4 {x, y, z, bits(word)},
 // word = (ns gap to the previous event << 2) | type, [n_events][batch]: 16 B per event, coalesced.
-#include "pekf_phase3.hpp"
+// Phase 2 in one launch, k_frontend_init, is here too; pekf_phase2.hpp states what it shares with the chunked
+// form (pekf_frontend_resume.hip).
+#include "pekf_phase2.hpp"
 
 namespace pekf {
 
-constexpr int kFeBlock = 256;
-// Non-temporal event loads (every event is read once per pass): k_frontend -1.7 %, phase 2's means
-// -5 % (profiles/r4/ntload/).
+// Non-temporal event loads (every event is read once per pass): k_frontend -1.7 % (profiles/r4/ntload/;
+// phase 2's PEKF_INIT_NTL is pekf_phase2.hpp's).
 #ifndef PEKF_FE_NTL
 #define PEKF_FE_NTL 1
-#endif
-#ifndef PEKF_INIT_NTL
-#define PEKF_INIT_NTL 1
 #endif
 
 // k_frontend's record queue: per group of kFeGroup lanes (one 128 B line of a gd / am row), a pool of
@@ -212,28 +210,19 @@ __global__ __launch_bounds__(64) void k_frontend(int64_t batch, int64_t n_events
     if (bad && err) atomicOr(err, bad);
 }
 
-// Phase 2 of the server's Parser (ProcessString, Parser.cpp:36-58; initialMeanAndCovariance,
-// :84-140; InitialValues.cpp): the first n_avg samples of each sensor type are averaged (a
-// sequential FP64 sum divided by n_avg) and their sample variance formed ((x - mean)^2 summed in
-// order, divided by n_avg - 1).  A sensor counts as initialised at its first sample after those
-// n_avg; the first event after all three are initialised builds the KalmanFilter (T0 = its time,
-// acc_0 / mag_0 = the raw means at that time), and every later phase-2 event moves the acc_0 / mag_0
-// time and previousT to its own (setAcc0 / setMag0, UpdateLatestPreviousTime).  So phase 3 starts
-// from init = {mean acc, mean mag} at t_init = the last phase-2 event's time -- exactly the inputs of
-// pekf_frontend_dev.  Same event planes as phase 3; two passes over them (the variance needs the
-// mean first, as InitialValues::compute_mean_and_variance has it).
-// Every message counts, whatever its sensor type: one no sensor takes (type 3) adds no sample but, once
-// all three are initialised, builds the filter or moves its time as any other (Parser.cpp:36-62).
-// EV64: FP64 events (the server's stod doubles are what it averages, Parser.cpp:23-25,84-140); their
-// times are absolute, and the no-message event (padding, ev64_none) is skipped.
+// Phase 2 of the server's Parser in one launch (pekf_phase2.hpp states the state machine): the means from its
+// first pass, then the sample variance of the first n_avg samples of each sensor type ((x - mean)^2 summed in
+// order, divided by n_avg - 1; initialMeanAndCovariance, Parser.cpp:84-140).  Same event planes as phase 3; two
+// passes over them (the variance needs the mean first, as InitialValues::compute_mean_and_variance has it).
+// EV64: FP64 events (double4 planes, PEKF_EV_F64_EVENTS).
 template <bool EV64 = false>
-__global__ __launch_bounds__(kFeBlock) void k_frontend_init(int64_t batch, int64_t n_events,
+__global__ __launch_bounds__(kInitBlock) void k_frontend_init(int64_t batch, int64_t n_events,
                                                             const std::conditional_t<EV64, double4, float4> *__restrict__ ev,
                                                             const int64_t *__restrict__ t_start, int n_avg,
                                                             double *__restrict__ init, int64_t *__restrict__ t_init,
                                                             double *__restrict__ stats, int32_t *__restrict__ ready) {
     using EvT = std::conditional_t<EV64, double4, float4>;
-    const int64_t b = (int64_t)blockIdx.x * kFeBlock + threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * kInitBlock + threadIdx.x;
     if (b >= batch) return;
     const uint32_t lane = (uint32_t)b;
     double sum[3][3] = {};  // [type][xyz]
@@ -243,7 +232,6 @@ __global__ __launch_bounds__(kFeBlock) void k_frontend_init(int64_t batch, int64
     int64_t t = t_start[b], t_last = t;
     // events come kInitRing rows at a time (pekf_phase3.hpp: load_event_block); the null events that pad
     // the last block are skipped by both passes
-    constexpr int kInitRing = 8;
     const int32_t n_ev = (int32_t)n_events;
     for (int32_t e0 = 0; e0 < n_ev; e0 += kInitRing) {
         EvT r[kInitRing];
@@ -334,14 +322,10 @@ using namespace pekf;
 extern "C" int pekf_frontend_init_ext_dev(int64_t batch, int64_t n_events, const void *ev_planes,
                                           const int64_t *t_start, int n_avg, double *init, int64_t *t_init,
                                           double *stats, int32_t *ready, uint32_t flags, void *stream) {
-    PEKF_CHECK_ARG(batch >= 0 && n_events >= 0, "negative size");
-    PEKF_CHECK_ARG(n_avg >= 2, "n_avg must be >= 2 (the variance divides by n_avg - 1)");
-    PEKF_CHECK_ARG(n_events < ((int64_t)1 << 30), "n_events must be < 2^30 per launch");
-    PEKF_CHECK_ARG((flags & ~(PEKF_EV_TIME_EVENTS | PEKF_EV_F64_EVENTS)) == 0, "unknown flags");
+    if (int st = check_init_args(batch, n_events, n_avg, flags, ev_planes, init, t_init, ready)) return st;
     if (batch == 0) return PEKF_OK;
-    PEKF_CHECK_ARG(ev_planes && t_start && init && t_init && ready, "null pointer");
-    PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
-    const dim3 grid(grid_for(batch, kFeBlock)), block(kFeBlock);
+    PEKF_CHECK_ARG(ev_planes && t_start, "null pointer");  // (stats may be null: the means alone)
+    const dim3 grid(grid_for(batch, kInitBlock)), block(kInitBlock);
     dispatch_bools(
         [&](auto ev64) {  // phase 2 always honours time events
             using Ev = std::conditional_t<ev64.value, double4, float4>;

@@ -1,39 +1,28 @@
 // pekf_frontend_resume.hip -- phase 2 fed in chunks (pekf_frontend_init_resume_dev,
-// pekf_frontend_init_state_bytes): k_frontend_init's first pass (pekf_frontend.hip) on the next rows of the same
-// phones' phase-2 plane, its per-phone running state kept in a device buffer between launches, in a file of
-// its own so that pekf_frontend.hip's object and listing hold the kernels they held.  The means alone: the
-// reference's variance is a second pass over the first n_avg samples once the mean is known, and a chunked
-// feed no longer has them.
-#include "pekf_phase3.hpp"
+// pekf_frontend_init_state_bytes): k_frontend_init's first pass (pekf_frontend.hip; pekf_phase2.hpp) on the next
+// rows of the same phones' phase-2 plane, its per-phone running state kept in a device buffer between launches,
+// in a file of its own so that pekf_frontend.hip's object and listing hold the kernels they held.  The means
+// alone: the reference's variance is a second pass over the first n_avg samples once the mean is known, and a
+// chunked feed no longer has them.
+#include "pekf_phase2.hpp"
 
 namespace pekf {
 
-constexpr int kFeInitBlock = 256;  // k_frontend_init's block
-#ifndef PEKF_INIT_NTL
-#define PEKF_INIT_NTL 1  // non-temporal event loads, as k_frontend_init's (profiles/r4/ntload/)
-#endif
-
 // What phase 2 holds for a phone between two rows (Parser::ProcessString's members, KFS/Parser.cpp:36-58):
 // the three sequential FP64 sums, the three sample counts, the three "initialised" flags, the "filter built"
-// flag and the two clocks (t: the f32 events' running clock; t_last: the time phase 3 starts from).
-//
-// One device buffer of phone-minor planes of 16 B per lane, [plane][batch], as LiveState's (pekf_live.hpp): a
-// wave's load or store of a plane is one contiguous 1 KB access.  Planes 0-3 the sums 0..7; 4 {sum 8, t};
-// 5 {t_last, cnt[0] | cnt[1] << 32}; 6 {cnt[2] | flags << 32, 0}: 112 B per phone.  Read once before the
-// event loop, written once after it.
+// flag and the two clocks (t: the f32 events' running clock; t_last: the time phase 3 starts from), in 7 planes
+// of 16 B per lane (pekf_phase3.hpp: state_plane).
+// Planes 0-3 the sums 0..7; 4 {sum 8, t}; 5 {t_last, cnt[0] | cnt[1] << 32}; 6 {cnt[2] | flags << 32, 0}: 112 B
+// per phone.  Read once before the event loop, written once after it.
 struct InitState {
     static constexpr int kPlanes = 7;
     static constexpr int kBytes = 16 * kPlanes;  // per phone
 
-    static __device__ __forceinline__ double2 *plane(void *state, int64_t batch, int64_t b, int p) {
-        return reinterpret_cast<double2 *>(state) + ((int64_t)p * batch + b);
-    }
-    // (the members are the kernel's own locals, arrays of one type each: held in one struct they went to scratch)
     static __device__ __forceinline__ void load(void *state, int64_t batch, int64_t b, double (&sum)[3][3], int (&cnt)[3],
                                                 bool (&done)[3], bool &kalman, int64_t &t, int64_t &t_last) {
         double2 v[kPlanes];
 #pragma unroll
-        for (int p = 0; p < kPlanes; ++p) v[p] = *plane(state, batch, b, p);
+        for (int p = 0; p < kPlanes; ++p) v[p] = *state_plane(state, batch, b, p);
 #pragma unroll
         for (int i = 0; i < 8; ++i) sum[i / 3][i % 3] = (i & 1) ? v[i / 2].y : v[i / 2].x;
         sum[2][2] = v[4].x;
@@ -58,21 +47,22 @@ struct InitState {
                                     make_double2(__longlong_as_double(t_last), __hiloint2double(cnt[1], cnt[0])),
                                     make_double2(__hiloint2double((int)flags, cnt[2]), 0.0)};
 #pragma unroll
-        for (int p = 0; p < kPlanes; ++p) *plane(state, batch, b, p) = v[p];
+        for (int p = 0; p < kPlanes; ++p) *state_plane(state, batch, b, p) = v[p];
     }
 };
 
-// k_frontend_init's first pass, statement for statement, on rows that continue a phone's stream: resume == 0
-// starts from t_start as the one launch does, resume != 0 from `state`.  The null events that pad a chunk's
-// last block of rows fall mid-stream here and move nothing: an FP64 no-message event is skipped, the f32 one
-// is a time event of step 0.  The outputs are the one launch's on the rows fed so far.
+// k_frontend_init's first pass, statement for statement (pekf_phase2.hpp says why it is not one function), on
+// rows that continue a phone's stream: resume == 0 starts from t_start as the one launch does, resume != 0 from
+// `state`.  The null events that pad a chunk's last block of rows fall mid-stream here and move nothing: an FP64
+// no-message event is skipped, the f32 one is a time event of step 0.  The outputs are the one launch's on the
+// rows fed so far.
 template <bool EV64>
-__global__ __launch_bounds__(kFeInitBlock) void k_frontend_init_resume(
+__global__ __launch_bounds__(kInitBlock) void k_frontend_init_resume(
     int64_t batch, int64_t n_events, const std::conditional_t<EV64, double4, float4> *__restrict__ ev,
     const int64_t *__restrict__ t_start, int n_avg, double *__restrict__ init, int64_t *__restrict__ t_init,
     int32_t *__restrict__ ready, void *__restrict__ state, int32_t resume) {
     using EvT = std::conditional_t<EV64, double4, float4>;
-    const int64_t b = (int64_t)blockIdx.x * kFeInitBlock + threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * kInitBlock + threadIdx.x;
     if (b >= batch) return;
     const uint32_t lane = (uint32_t)b;
     double sum[3][3] = {};  // [type][xyz]
@@ -89,7 +79,6 @@ __global__ __launch_bounds__(kFeInitBlock) void k_frontend_init_resume(
     } else {
         t = t_last = t_start[b];
     }
-    constexpr int kInitRing = 8;
     const int32_t n_ev = (int32_t)n_events;
     for (int32_t e0 = 0; e0 < n_ev; e0 += kInitRing) {
         EvT r[kInitRing];
@@ -141,8 +130,6 @@ __global__ __launch_bounds__(kFeInitBlock) void k_frontend_init_resume(
 
 using namespace pekf;
 
-static bool init_flags_ok(uint32_t flags) { return (flags & ~(PEKF_EV_TIME_EVENTS | PEKF_EV_F64_EVENTS)) == 0; }
-
 static_assert(sizeof(long long) == sizeof(int64_t), "pekf_frontend_init_state_bytes returns 64 bits");
 extern "C" long long int pekf_frontend_init_state_bytes(int64_t batch, uint32_t flags) {
     if (batch < 0 || !init_flags_ok(flags)) return -1;
@@ -152,17 +139,12 @@ extern "C" long long int pekf_frontend_init_state_bytes(int64_t batch, uint32_t 
 extern "C" int pekf_frontend_init_resume_dev(int64_t batch, int64_t n_events, const void *ev_planes,
                                              const int64_t *t_start, int n_avg, double *init, int64_t *t_init,
                                              int32_t *ready, uint32_t flags, void *state, int resume, void *stream) {
-    PEKF_CHECK_ARG(batch >= 0 && n_events >= 0, "negative size");
-    PEKF_CHECK_ARG(n_avg >= 2, "n_avg must be >= 2 (as pekf_frontend_init_dev)");
-    PEKF_CHECK_ARG(n_events < ((int64_t)1 << 30), "n_events must be < 2^30 per launch");
-    PEKF_CHECK_ARG(init_flags_ok(flags), "unknown flags");
+    if (int st = check_init_args(batch, n_events, n_avg, flags, ev_planes, init, t_init, ready)) return st;
     PEKF_CHECK_ARG(state && (uintptr_t)state % 16 == 0, "state must be a 16-byte aligned pointer");
     if (batch == 0) return PEKF_OK;
     PEKF_CHECK_ARG(batch < ((int64_t)1 << 28), "batch must be < 2^28 phones per launch");
-    PEKF_CHECK_ARG(init && t_init && ready && (resume || t_start), "null pointer");
-    PEKF_CHECK_ARG(n_events == 0 || ev_planes, "null pointer");
-    PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
-    const dim3 grid(grid_for(batch, kFeInitBlock)), block(kFeInitBlock);
+    PEKF_CHECK_ARG(resume || t_start, "null pointer");  // read when a session starts
+    const dim3 grid(grid_for(batch, kInitBlock)), block(kInitBlock);
     dispatch_bools(
         [&](auto ev64) {  // phase 2 always honours time events
             using Ev = std::conditional_t<ev64.value, double4, float4>;

@@ -28,36 +28,26 @@
 
 using namespace pekf;
 
-// the checks behind every pekf_live_* entry; traj_rows == 0: the kernels without trajectory output, which
-// this file instantiates (and no others: tests/test_omod_listing.py counts them)
-static int launch_live(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
-                       const int64_t *t_init, double alpha, double *X, double *P, double q, double r, int32_t *counts,
-                       double *refs, uint32_t flags, double *traj, double *traj_dt, int64_t traj_rows, int *dev_error,
-                       void *stream) {
-    if (int st = check_live_flags(batch, n_events, flags, traj, traj_dt, traj_rows)) return st;
-    if (batch == 0) return PEKF_OK;
-    if (int st = check_live_launch(batch, n_events, ev_planes, init, t_init, X, P, r, counts, refs)) return st;
-    (void)dev_error;  // every record's dt is applied (escaped ones from the queue's side entries)
-    if (traj_rows > 0)  // the TRAJ twins: pekf_live_traj.hip
-        return launch_live_traj(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, traj,
-                                traj_dt, (int32_t)traj_rows, as_stream(stream));
-    return launch_k_live<false>(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, nullptr,
-                                nullptr, 0, as_stream(stream));
-}
-
+// Every one-shot entry ends here.  traj_rows == 0: the kernels without trajectory output, which this file
+// instantiates (and no others: tests/test_omod_listing.py counts them); their TRAJ twins are pekf_live_traj.hip's.
 extern "C" int pekf_live_traj_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
                                   const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
                                   int32_t *counts, double *refs, uint32_t flags, double *traj, double *traj_dt,
                                   int64_t traj_rows, int *dev_error, void *stream) {
-    return launch_live(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, traj, traj_dt,
-                       traj_rows, dev_error, stream);
+    const LiveCall c = {batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags,
+                        traj, traj_dt, traj_rows, as_stream(stream)};
+    if (int st = check_live_flags(c)) return st;
+    if (batch == 0) return PEKF_OK;
+    if (int st = check_live_launch(c)) return st;
+    (void)dev_error;  // every record's dt is applied (escaped ones from the queue's side entries)
+    return traj_rows > 0 ? launch_live_traj(c) : launch_k_live<false>(c);
 }
 
 extern "C" int pekf_live_ext_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
                                  const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
                                  int32_t *counts, double *refs, uint32_t flags, int *dev_error, void *stream) {
-    return launch_live(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, nullptr,
-                       nullptr, 0, dev_error, stream);
+    return pekf_live_traj_dev(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, nullptr,
+                              nullptr, 0, dev_error, stream);
 }
 
 extern "C" int pekf_live_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,

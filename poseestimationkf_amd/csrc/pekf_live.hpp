@@ -1,7 +1,8 @@
 // pekf_live.hpp -- k_live, the fused front-end + filter kernel, and its record queue (see pekf_live.hip,
 // which instantiates the kernels without trajectory output; pekf_live_traj.hip instantiates their TRAJ twins,
 // pekf_live_resume.hip the resumable kernels of a session fed in chunks, pekf_live_join.hip those whose filters
-// join the session one by one).
+// join the session one by one).  The host side every pekf_live_* entry shares closes the file: LiveCall (the
+// entries' common arguments), their checks, and the one launcher, launch_k_live<TRAJ, RESUME, JOIN>.
 #pragma once
 #include "pekf_phase3.hpp"
 #include "pekf_step.hpp"
@@ -267,16 +268,12 @@ struct LiveState {
             mv<LOAD>(fe.t, d[k++]);
         }
     }
-    static __device__ __forceinline__ double2 *plane(void *state, int64_t batch, int64_t b, int p) {
-        return reinterpret_cast<double2 *>(state) + ((int64_t)p * batch + b);
-    }
-
     static __device__ __forceinline__ void load(void *state, int64_t batch, int64_t b, Fe &fe, double *x,
                                                 Sym4T<double> &N, int32_t &total) {
         double d[kDoubles];
 #pragma unroll
         for (int p = 0; p < kDoubles / 2; ++p) {
-            const double2 v = *plane(state, batch, b, p);
+            const double2 v = *state_plane(state, batch, b, p);
             d[2 * p] = v.x;
             d[2 * p + 1] = v.y;
         }
@@ -288,7 +285,7 @@ struct LiveState {
         if constexpr (!EV64) {
             float4 s[4];
 #pragma unroll
-            for (int p = 0; p < 4; ++p) s[p] = *reinterpret_cast<const float4 *>(plane(state, batch, b, kDoubles / 2 + p));
+            for (int p = 0; p < 4; ++p) s[p] = *reinterpret_cast<const float4 *>(state_plane(state, batch, b, kDoubles / 2 + p));
             fe.acc0 = {s[0].x, s[0].y, s[0].z}; fe.mag0 = {s[0].w, s[1].x, s[1].y};
             fe.acc1 = {s[1].z, s[1].w, s[2].x}; fe.mag1 = {s[2].y, s[2].z, s[2].w};
             fe.gyro = {s[3].x, s[3].y, s[3].z};
@@ -297,7 +294,7 @@ struct LiveState {
     // the flag word's bit 5 (k_live<..., JOIN>): this lane has joined the session -- its state is to be resumed
     static constexpr uint32_t kJoined = 32u;
     static __device__ __forceinline__ bool joined(void *state, int64_t batch, int64_t b) {
-        return ((uint32_t)__double2loint(plane(state, batch, b, kDoubles / 2 - 1)->y) & kJoined) != 0;
+        return ((uint32_t)__double2loint(state_plane(state, batch, b, kDoubles / 2 - 1)->y) & kJoined) != 0;
     }
     static __device__ __forceinline__ void store(void *state, int64_t batch, int64_t b, Fe &fe, double *x,
                                                  Sym4T<double> &N, int32_t total, uint32_t mark = 0u) {
@@ -307,14 +304,14 @@ struct LiveState {
                                (fe.acc1_set ? 8u : 0u) | (fe.mag1_set ? 16u : 0u) | mark;
         d[kDoubles - 1] = __hiloint2double(total, (int)flags);
 #pragma unroll
-        for (int p = 0; p < kDoubles / 2; ++p) *plane(state, batch, b, p) = make_double2(d[2 * p], d[2 * p + 1]);
+        for (int p = 0; p < kDoubles / 2; ++p) *state_plane(state, batch, b, p) = make_double2(d[2 * p], d[2 * p + 1]);
         if constexpr (!EV64) {
             const float4 s[4] = {make_float4(fe.acc0.x, fe.acc0.y, fe.acc0.z, fe.mag0.x),
                                  make_float4(fe.mag0.y, fe.mag0.z, fe.acc1.x, fe.acc1.y),
                                  make_float4(fe.acc1.z, fe.mag1.x, fe.mag1.y, fe.mag1.z),
                                  make_float4(fe.gyro.x, fe.gyro.y, fe.gyro.z, 0.f)};
 #pragma unroll
-            for (int p = 0; p < 4; ++p) *reinterpret_cast<float4 *>(plane(state, batch, b, kDoubles / 2 + p)) = s[p];
+            for (int p = 0; p < 4; ++p) *reinterpret_cast<float4 *>(state_plane(state, batch, b, kDoubles / 2 + p)) = s[p];
         }
     }
 };
@@ -516,58 +513,78 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     store_state<false>(Xio, Pio, b, batch, x, P);
 }
 
+// What every pekf_live_* entry is handed (include/pekf.h: pekf_live_traj_dev's arguments), filled once by the
+// entry and passed to the checks and the launcher below.
+struct LiveCall {
+    int64_t batch, n_events;
+    const void *ev_planes;
+    const double *init;
+    const int64_t *t_init;
+    double alpha;
+    double *X, *P;
+    double q, r;
+    int32_t *counts;
+    double *refs;
+    uint32_t flags;
+    double *traj, *traj_dt;  // read only when traj_rows > 0
+    int64_t traj_rows;
+    hipStream_t stream;
+};
 
-// One launch of k_live<TE, R64, EV64, TRAJ> by pekf_live_ext_dev's flags (checked by the caller), all five
-// combinations.  TRAJ = false is instantiated by pekf_live.hip, TRAJ = true by pekf_live_traj.hip alone, so
-// each file's listing holds five kernels.
-template <bool TRAJ>
-int launch_k_live(int64_t batch, int64_t n_events, const void *ev_planes, const double *init, const int64_t *t_init,
-                  double alpha, double *X, double *P, double q, double r, int32_t *counts, double *refs,
-                  uint32_t flags, double *traj, double *traj_dt, int32_t traj_rows, hipStream_t stream) {
-    const dim3 grid(grid_for(batch, kRunBlock)), block(kRunBlock);
-    auto launch = [&](auto kernel, const auto *ev) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, stream, batch, n_events, ev, init, t_init, alpha, q, r, X, P, counts,
-                           refs, traj, traj_dt, traj_rows, nullptr, 0);
-    };
-    if (flags & PEKF_EV_F64_EVENTS)  // the one FP64-event variant
-        launch(k_live<false, false, true, TRAJ>, static_cast<const double4 *>(ev_planes));
-    else
-        dispatch_bools(
-            [&](auto te, auto r64) {
-                launch(k_live<te.value, r64.value, false, TRAJ>, static_cast<const float4 *>(ev_planes));
-            },
-            (flags & PEKF_EV_TIME_EVENTS) != 0, (flags & PEKF_EV_F32_RECORDS) == 0);
-    return launched("k_live");
-}
 // The argument checks every pekf_live_* entry shares, in two halves: sizes, flags and the trajectory arguments
 // (before the batch == 0 return), then the launch's limits and pointers (after it).
-static inline int check_live_flags(int64_t batch, int64_t n_events, uint32_t flags, const double *traj,
-                                   const double *traj_dt, int64_t traj_rows) {
-    PEKF_CHECK_ARG(batch >= 0 && n_events >= 0, "negative size");
-    PEKF_CHECK_ARG((flags & ~(PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS | PEKF_EV_F64_EVENTS)) == 0, "unknown flags");
-    const bool ev64 = (flags & PEKF_EV_F64_EVENTS) != 0;
-    PEKF_CHECK_ARG(!ev64 || (flags & (PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS)) == 0,
+static inline int check_live_flags(const LiveCall &c) {
+    PEKF_CHECK_ARG(c.batch >= 0 && c.n_events >= 0, "negative size");
+    PEKF_CHECK_ARG((c.flags & ~(PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS | PEKF_EV_F64_EVENTS)) == 0, "unknown flags");
+    const bool ev64 = (c.flags & PEKF_EV_F64_EVENTS) != 0;
+    PEKF_CHECK_ARG(!ev64 || (c.flags & (PEKF_EV_TIME_EVENTS | PEKF_EV_F32_RECORDS)) == 0,
                    "PEKF_EV_F64_EVENTS takes no other flag (FP64 events carry their times; their records are FP64)");
-    PEKF_CHECK_ARG(traj_rows >= 0 && traj_rows < ((int64_t)1 << 31), "traj_rows must be >= 0 and < 2^31");
-    PEKF_CHECK_ARG(traj_rows == 0 || (traj && (uintptr_t)traj % 16 == 0),
+    PEKF_CHECK_ARG(c.traj_rows >= 0 && c.traj_rows < ((int64_t)1 << 31), "traj_rows must be >= 0 and < 2^31");
+    PEKF_CHECK_ARG(c.traj_rows == 0 || (c.traj && (uintptr_t)c.traj % 16 == 0),
                    "traj must be a 16-byte aligned pointer when traj_rows > 0");
-    PEKF_CHECK_ARG(traj_rows == 0 || (uintptr_t)traj_dt % 8 == 0, "misaligned traj_dt");
+    PEKF_CHECK_ARG(c.traj_rows == 0 || (uintptr_t)c.traj_dt % 8 == 0, "misaligned traj_dt");
     return PEKF_OK;
 }
-static inline int check_live_launch(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
-                                    const int64_t *t_init, const double *X, const double *P, double r,
-                                    const int32_t *counts, const double *refs) {
-    PEKF_CHECK_ARG(batch < ((int64_t)1 << 28), "batch must be < 2^28 filters per launch");
-    PEKF_CHECK_ARG(n_events < ((int64_t)1 << 30), "n_events must be < 2^30 per launch");
-    PEKF_CHECK_ARG(ev_planes && init && t_init && X && P && counts && refs, "null pointer");
-    PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
-    PEKF_CHECK_ARG(r > 0.0, "r must be > 0 (S = P- + rI must be SPD)");
+static inline int check_live_launch(const LiveCall &c) {
+    PEKF_CHECK_ARG(c.batch < ((int64_t)1 << 28), "batch must be < 2^28 filters per launch");
+    PEKF_CHECK_ARG(c.n_events < ((int64_t)1 << 30), "n_events must be < 2^30 per launch");
+    PEKF_CHECK_ARG(c.ev_planes && c.init && c.t_init && c.X && c.P && c.counts && c.refs, "null pointer");
+    PEKF_CHECK_ARG((uintptr_t)c.ev_planes % 16 == 0, "misaligned event planes");
+    PEKF_CHECK_ARG(c.r > 0.0, "r must be > 0 (S = P- + rI must be SPD)");
     return PEKF_OK;
+}
+
+// The one launch of k_live<TE, R64, EV64, TRAJ, RESUME, JOIN>, by the call's flags (checked by the entry).  Each
+// instantiation names the kernels its file holds, and no others (tests/test_omod_listing.py counts them):
+//   <TRAJ>              the five of pekf_live_ext_dev's flags, TE x R64 and the FP64-event form (pekf_live.hip
+//                       without TRAJ, pekf_live_traj.hip with it);
+//   <TRAJ, true>        a resumable launch takes FP64 records, so TE and the FP64-event form (pekf_live_resume.hip);
+//   <TRAJ, true, true>  filters join a session of FP64 events only (pekf_live_join.hip).
+// Without TRAJ the kernels read none of the trajectory arguments and are handed none.
+template <bool TRAJ, bool RESUME = false, bool JOIN = false>
+int launch_k_live(const LiveCall &c, void *state = nullptr, int32_t resume = 0) {
+    const dim3 grid(grid_for(c.batch, kRunBlock)), block(kRunBlock);
+    auto launch = [&](auto kernel, const auto *ev) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, c.stream, c.batch, c.n_events, ev, c.init, c.t_init, c.alpha, c.q, c.r,
+                           c.X, c.P, c.counts, c.refs, TRAJ ? c.traj : nullptr, TRAJ ? c.traj_dt : nullptr,
+                           TRAJ ? (int32_t)c.traj_rows : 0, state, resume);
+    };
+    if (JOIN || (c.flags & PEKF_EV_F64_EVENTS))  // the one FP64-event variant
+        launch(k_live<false, false, true, TRAJ, RESUME, JOIN>, static_cast<const double4 *>(c.ev_planes));
+    else if constexpr (RESUME && !JOIN)
+        dispatch_bools(
+            [&](auto te) { launch(k_live<te.value, true, false, TRAJ, true>, static_cast<const float4 *>(c.ev_planes)); },
+            (c.flags & PEKF_EV_TIME_EVENTS) != 0);
+    else if constexpr (!RESUME)
+        dispatch_bools(
+            [&](auto te, auto r64) {
+                launch(k_live<te.value, r64.value, false, TRAJ>, static_cast<const float4 *>(c.ev_planes));
+            },
+            (c.flags & PEKF_EV_TIME_EVENTS) != 0, (c.flags & PEKF_EV_F32_RECORDS) == 0);
+    return launched(JOIN ? "k_live (joining)" : RESUME ? "k_live (resumable)" : "k_live");
 }
 
 // launch_k_live<true> (pekf_live_traj.hip)
-int launch_live_traj(int64_t batch, int64_t n_events, const void *ev_planes, const double *init, const int64_t *t_init,
-                     double alpha, double *X, double *P, double q, double r, int32_t *counts, double *refs,
-                     uint32_t flags, double *traj, double *traj_dt, int32_t traj_rows, hipStream_t stream);
+int launch_live_traj(const LiveCall &c);
 
 }  // namespace pekf

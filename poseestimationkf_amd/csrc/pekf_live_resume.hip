@@ -9,25 +9,6 @@
 
 using namespace pekf;
 
-template <bool TRAJ>
-static int launch_k_live_resume(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
-                                const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
-                                int32_t *counts, double *refs, uint32_t flags, double *traj, double *traj_dt,
-                                int32_t traj_rows, void *state, int32_t resume, hipStream_t stream) {
-    const dim3 grid(grid_for(batch, kRunBlock)), block(kRunBlock);
-    auto launch = [&](auto kernel, const auto *ev) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, stream, batch, n_events, ev, init, t_init, alpha, q, r, X, P, counts,
-                           refs, traj, traj_dt, traj_rows, state, resume);
-    };
-    if (flags & PEKF_EV_F64_EVENTS)
-        launch(k_live<false, false, true, TRAJ, true>, static_cast<const double4 *>(ev_planes));
-    else
-        dispatch_bools(
-            [&](auto te) { launch(k_live<te.value, true, false, TRAJ, true>, static_cast<const float4 *>(ev_planes)); },
-            (flags & PEKF_EV_TIME_EVENTS) != 0);
-    return launched("k_live (resumable)");
-}
-
 // the flags a session state exists for: none, PEKF_EV_TIME_EVENTS (the same state) or PEKF_EV_F64_EVENTS alone
 static bool resume_flags_ok(uint32_t flags) {
     return flags == 0 || flags == PEKF_EV_TIME_EVENTS || flags == PEKF_EV_F64_EVENTS;
@@ -43,21 +24,19 @@ extern "C" int pekf_live_resume_dev(int64_t batch, int64_t n_events, const void 
                                     const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
                                     int32_t *counts, double *refs, uint32_t flags, void *state, int resume,
                                     double *traj, double *traj_dt, int64_t traj_rows, int *dev_error, void *stream) {
-    if (int st = check_live_flags(batch, n_events, flags, traj, traj_dt, traj_rows)) return st;
+    const LiveCall c = {batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags,
+                        traj, traj_dt, traj_rows, as_stream(stream)};
+    if (int st = check_live_flags(c)) return st;
     PEKF_CHECK_ARG((flags & PEKF_EV_F32_RECORDS) == 0,
                    "a resumable launch takes FP64 records (PEKF_EV_F32_RECORDS is the one-shot split pipeline's)");
     PEKF_CHECK_ARG(state && (uintptr_t)state % 16 == 0, "state must be a 16-byte aligned pointer");
     if (batch == 0) return PEKF_OK;
-    if (int st = check_live_launch(batch, n_events, ev_planes, init, t_init, X, P, r, counts, refs)) return st;
+    if (int st = check_live_launch(c)) return st;
     (void)dev_error;
     if (resume && n_events == 0) {  // nothing to continue with: the state, X and P stay, no record is counted
-        PEKF_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)batch, as_stream(stream)));
+        PEKF_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)batch, c.stream));
         return PEKF_OK;
     }
-    if (traj_rows > 0)
-        return launch_k_live_resume<true>(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs,
-                                          flags, traj, traj_dt, (int32_t)traj_rows, state, resume != 0,
-                                          as_stream(stream));
-    return launch_k_live_resume<false>(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags,
-                                       nullptr, nullptr, 0, state, resume != 0, as_stream(stream));
+    return traj_rows > 0 ? launch_k_live<true, true>(c, state, resume != 0)
+                         : launch_k_live<false, true>(c, state, resume != 0);
 }

@@ -5,11 +5,6 @@
 
 namespace pekf {
 
-int launch_live_traj(int64_t batch, int64_t n_events, const void *ev_planes, const double *init, const int64_t *t_init,
-                     double alpha, double *X, double *P, double q, double r, int32_t *counts, double *refs,
-                     uint32_t flags, double *traj, double *traj_dt, int32_t traj_rows, hipStream_t stream) {
-    return launch_k_live<true>(batch, n_events, ev_planes, init, t_init, alpha, X, P, q, r, counts, refs, flags, traj,
-                               traj_dt, traj_rows, stream);
-}
+int launch_live_traj(const LiveCall &c) { return launch_k_live<true>(c); }
 
 }  // namespace pekf

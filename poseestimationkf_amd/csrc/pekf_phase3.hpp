@@ -22,8 +22,8 @@
 // the same code for both.
 //
 // The event accessors (event_type, is_message, load_event, null_event) and the two readers of an event
-// plane (load_event_block, event_ring) are here too: phases 1 and 2 (pekf_magcal.hip, k_frontend_init)
-// read the same planes.
+// plane (load_event_block, event_ring) are here too: phases 1 and 2 (pekf_magcal.hip, pekf_phase2.hpp)
+// read the same planes.  So is state_plane, the addressing of the state a session fed in chunks keeps.
 #pragma once
 
 #include "pekf_internal.hpp"
@@ -209,6 +209,13 @@ __device__ __forceinline__ void event_ring(const EvT *ev, int64_t batch, uint32_
             after_block(e0 + kRing >= n_ev);
         }
     }
+}
+
+// A session's device state between two launches (LiveState, pekf_live.hpp; InitState, pekf_frontend_resume.hip):
+// lane-minor planes of 16 B per lane, [plane][batch], so a wave's load or store of a plane is one contiguous
+// 1 KB access.  Lane b's 16 bytes of plane p.
+__device__ __forceinline__ double2 *state_plane(void *state, int64_t batch, int64_t b, int p) {
+    return reinterpret_cast<double2 *>(state) + ((int64_t)p * batch + b);
 }
 
 // With f32 events (S = F3) the state machine moves samples as f32 (one select per component instead

@@ -5,6 +5,7 @@ filter runs in the HIP kernels of libpekf.so.
 """
 from __future__ import annotations
 
+import copy
 import ctypes
 import os
 import types
@@ -867,7 +868,101 @@ def chunk_trajectory_rows(trajectory, n_events):
     return (int(n_events) + 2) // 3 if trajectory is True else trajectory_rows(trajectory, n_events)
 
 
-class LiveSession:
+class _ChunkedSession:
+    """A session fed in chunks, what LiveSession and PhoneSession share: the filters it refuses, the host
+    bookkeeping (the summed counts, the running record times), what follows a chunk's launch, and snapshot /
+    restore.  A subclass allocates its DeviceBuffers as self._<name> (_cnt and _refs among them), launches, and
+    states three things: _BUFFERS, the buffers a snapshot carries (name -> None: its bytes as uint8, or n: (K, n)
+    float64); _FIELDS, the constructor's scalars it carries; _from_snapshot, the empty session restore fills."""
+
+    _BUFFERS, _FIELDS = {}, ()
+
+    def __init__(self, filters):
+        if filters.layout != "aos" or filters.flags & RUN_MIXED_PRECISION:
+            raise ValueError("the fused front-end + filter kernel runs the FP64 filter on AoS state")
+        K = filters.batch
+        self.filters, self.batch = filters, K
+        self._book = dict(started=False, t_init=np.zeros(K, np.int64), dt_sum=np.zeros(K),
+                          total_counts=np.zeros(K, np.int64))
+
+    @property
+    def total_counts(self):
+        """(K,) int64: the records each filter has applied since the session began"""
+        return self._book["total_counts"].copy()
+
+    @property
+    def refs(self):
+        """(K, 6) the filters' acc0 / mag0 as of the last chunk (written by every launch; before the first, from
+        a zero-row one; NaN for a phone that is not ready)"""
+        if not self._book["started"]:
+            self._feed_no_rows()
+        return self._refs.download((self.batch, 6), np.float64)
+
+    @staticmethod
+    def _rows_in(planes, n, offset, row_bytes):
+        """Refuses n rows of row_bytes, `offset` bytes into the DeviceBuffer planes, that are not all inside it"""
+        if n < 0 or offset < 0 or offset % 16 or (n > 0 and (planes is None or offset + n * row_bytes > planes.nbytes)):
+            raise ValueError("offset / rows outside the planes buffer (or offset not a multiple of 16)")
+
+    def _after_launch(self, tj):
+        """What follows a chunk's launches: the sync, the chunk's counts, the bookkeeping.  Returns (counts,), or
+        with a trajectory asked for (tj: the launch's _Trajectory) (counts, its dict)."""
+        K, book = self.batch, self._book
+        check(lib.pekf_device_sync())
+        book["started"] = True
+        counts = self._cnt.download((K,), np.int32)
+        self._first_records((book["total_counts"] == 0) & (counts > 0))
+        book["total_counts"] += counts
+        if not tj.wanted:
+            book["dt_sum"] = np.where(counts > 0, np.nan, book["dt_sum"])   # these records' dts were not asked for
+            return (counts,)
+        return counts, self._chunk_result(tj.result(np.zeros(K)), counts)
+
+    def _first_records(self, first):
+        """first (K,) bool: the filters whose first record of the session was applied in this chunk"""
+
+    def _chunk_result(self, out, counts):
+        """The chunk's trajectory dict with record_times_ns continuing from the session's running record time: per
+        filter t_init + the running sum of every dt so far, summed in the order one launch's cumsum would.  A
+        filter whose earlier records' dts were not all downloaded (a chunk fed without a trajectory, or with a
+        row cap below its count) has NaN times from then on."""
+        book, dt = self._book, out["record_dt_ns"]
+        run = np.cumsum(np.concatenate([book["dt_sum"][None, :], dt], axis=0), axis=0)
+        out["record_times_ns"] = book["t_init"].astype(np.float64)[None, :] + run[1:]
+        seen = np.minimum(counts, len(dt))
+        last = run[seen, np.arange(self.batch)]
+        book["dt_sum"] = np.where(counts > len(dt), np.nan, last)
+        return out
+
+    def snapshot(self):
+        """The session as host data: dict(batch, q, r, the class's scalars, its device buffers -- the session
+        state(s) as bytes (uint8 arrays) -- X, P and the host-side bookkeeping).  restore continues from it on
+        another BatchedEKF or device."""
+        K = self.batch
+        X, P = self.filters.get_state()
+        snap = dict(batch=K, q=self.filters.q, r=self.filters.r, X=X, P=P, book=copy.deepcopy(self._book))
+        snap.update((name, getattr(self, name)) for name in self._FIELDS)
+        for name, cols in self._BUFFERS.items():
+            buf = getattr(self, "_" + name)
+            snap[name] = buf.download((buf.nbytes,), np.uint8) if cols is None else buf.download((K, cols), np.float64)
+        return snap
+
+    @classmethod
+    def restore(cls, filters, snapshot):
+        """A session that continues `snapshot` on `filters` (same batch, q and r; set the device first to move a
+        shard): its X / P are set to the snapshot's, the buffers are uploaded as they were."""
+        s = snapshot
+        if filters.batch != s["batch"] or (filters.q, filters.r) != (s["q"], s["r"]):
+            raise ValueError("restore needs a BatchedEKF of the snapshot's batch, q and r")
+        self = cls._from_snapshot(filters, s)
+        filters.set_state(s["X"], s["P"])
+        for name in cls._BUFFERS:
+            getattr(self, "_" + name).upload(s[name])
+        self._book = copy.deepcopy(s["book"])
+        return self
+
+
+class LiveSession(_ChunkedSession):
     """A live session fed in chunks (pekf_live_resume_dev): the phones' phase-3 events as they arrive, a launch
     per chunk, the front-end's and the filter's state carried between them on the device.  However the events are
     cut into chunks, X, P, refs, the summed counts and the concatenated trajectory rows have the bits of
@@ -879,13 +974,14 @@ class LiveSession:
     of phase 2's init (K, 6) and init_mag None (_launch_phase2's); t_init (K,) int64 host array or DeviceBuffer.
     events: "f32" or "f64", fixed for the session (records are FP64 either way)."""
 
+    _BUFFERS, _FIELDS = dict(state=None, init=6, refs=6), ("events", "alpha")
+
     def __init__(self, filters, init_acc, init_mag, t_init, alpha=0.1, events="f32"):
         if events not in EVENT_FORMS:
             raise ValueError("events must be 'f32' or 'f64'")
-        if filters.layout != "aos" or filters.flags & RUN_MIXED_PRECISION:
-            raise ValueError("the fused front-end + filter kernel runs the FP64 filter on AoS state")
-        K = filters.batch
-        self.filters, self.batch, self.alpha, self.events = filters, K, float(alpha), events
+        super().__init__(filters)
+        K = self.batch
+        self.alpha, self.events = float(alpha), events
         self._form = EV_F64_EVENTS if events == "f64" else 0
         if isinstance(init_acc, DeviceBuffer):
             self._init = init_acc
@@ -898,28 +994,18 @@ class LiveSession:
         else:
             t_host = np.ascontiguousarray(t_init, np.int64).reshape(K).copy()
             self._t_init = DeviceBuffer(8 * K).upload(t_host)
-        self._alloc()
-        self._book = dict(started=False, t_init=t_host, last_times=t_host.copy(), dt_sum=np.zeros(K),
-                          total_counts=np.zeros(K, np.int64))
-
-    def _alloc(self):
-        K = self.batch
         nbytes = int(lib.pekf_live_state_bytes(K, self._form))
         if nbytes < 0:
             raise ValueError("no session state for these flags")
         self._state, self._cnt, self._refs = DeviceBuffer(nbytes), DeviceBuffer(4 * K), DeviceBuffer(48 * K)
+        self._book.update(t_init=t_host, last_times=t_host.copy())
 
-    @property
-    def total_counts(self):
-        """(K,) int64: the records each filter has applied since the session began"""
-        return self._book["total_counts"].copy()
+    @classmethod
+    def _from_snapshot(cls, filters, s):   # (init: an empty buffer, uploaded with the others)
+        return cls(filters, DeviceBuffer(48 * s["batch"]), None, s["book"]["t_init"], s["alpha"], s["events"])
 
-    @property
-    def refs(self):
-        """(K, 6) the filters' acc0 / mag0 (written by every launch; before the first, from a zero-event one)"""
-        if not self._book["started"]:
-            self.feed_planes(self._state, 0)
-        return self._refs.download((self.batch, 6), np.float64)
+    def _feed_no_rows(self):
+        self.feed_planes(self._state, 0)   # (no rows: any valid pointer, none is read)
 
     def pack_chunk(self, ev):
         """A chunk's rows (types / values / times, optionally values64) -> (host planes, PEKF_EV_* flags) in the
@@ -949,65 +1035,19 @@ class LiveSession:
         """n_events packed rows ([n_events][K] float4, or double4 for an FP64-event session) of the DeviceBuffer
         `planes`, starting `offset` bytes into it: row ranges of one resident plane are fed without copies.
         flags: EV_TIME_EVENTS if these rows hold time events (it may differ from chunk to chunk)."""
-        K, book = self.batch, self._book
+        K, f = self.batch, self.filters
         n_events, flags = int(n_events), int(flags) | self._form
-        row = K * (32 if self._form else 16)
-        if offset < 0 or offset % 16 or (n_events > 0 and offset + n_events * row > planes.nbytes):
-            raise ValueError("offset / n_events outside the planes buffer (or offset not a multiple of 16)")
+        self._rows_in(planes, n_events, offset, K * (32 if self._form else 16))
         tj = _Trajectory(chunk_trajectory_rows(trajectory, n_events) if trajectory is True else trajectory, n_events, K)
-        f = self.filters
         check(lib.pekf_live_resume_dev(K, n_events, planes.ptr + offset, self._init.ptr, self._t_init.ptr, self.alpha,
                                        f.X.ptr, f.P.ptr, f.q, f.r, self._cnt.ptr, self._refs.ptr, flags,
-                                       self._state.ptr, int(book["started"]), tj.traj.ptr if tj.rows else None,
+                                       self._state.ptr, int(self._book["started"]), tj.traj.ptr if tj.rows else None,
                                        tj.dt.ptr if tj.rows else None, tj.rows, None, None))
-        check(lib.pekf_device_sync())
-        book["started"] = True
-        counts = self._cnt.download((K,), np.int32)
-        book["total_counts"] += counts
-        if not tj.wanted:
-            book["dt_sum"] = np.where(counts > 0, np.nan, book["dt_sum"])   # these records' dts were not asked for
-            return counts
-        return counts, self._chunk_result(tj.result(np.zeros(K)), counts)
-
-    def _chunk_result(self, out, counts):
-        """The chunk's trajectory dict with record_times_ns continuing from the session's running record time: per
-        filter t_init + the running sum of every dt so far, summed in the order one launch's cumsum would.  A
-        filter whose earlier records' dts were not all downloaded (a chunk fed without a trajectory, or with a
-        row cap below its count) has NaN times from then on."""
-        book, dt = self._book, out["record_dt_ns"]
-        run = np.cumsum(np.concatenate([book["dt_sum"][None, :], dt], axis=0), axis=0)
-        out["record_times_ns"] = book["t_init"].astype(np.float64)[None, :] + run[1:]
-        seen = np.minimum(counts, len(dt))
-        last = run[seen, np.arange(self.batch)]
-        book["dt_sum"] = np.where(counts > len(dt), np.nan, last)
-        return out
-
-    def snapshot(self):
-        """The session as host data: dict(state (bytes of the device state as a uint8 array), X, P, refs and the
-        host-side bookkeeping).  LiveSession.restore continues from it on another BatchedEKF or device."""
-        K, book = self.batch, self._book
-        X, P = self.filters.get_state()
-        return dict(batch=K, events=self.events, alpha=self.alpha, q=self.filters.q, r=self.filters.r,
-                    state=self._state.download((self._state.nbytes,), np.uint8), X=X, P=P,
-                    init=self._init.download((K, 6), np.float64), refs=self._refs.download((K, 6), np.float64),
-                    book={k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in book.items()})
-
-    @classmethod
-    def restore(cls, filters, snapshot):
-        """A session that continues `snapshot` on `filters` (same batch, q and r; set the device first to move a
-        shard): its X / P are set to the snapshot's, the state is uploaded as it was."""
-        s = snapshot
-        if filters.batch != s["batch"] or (filters.q, filters.r) != (s["q"], s["r"]):
-            raise ValueError("restore needs a BatchedEKF of the snapshot's batch, q and r")
-        self = cls(filters, s["init"][:, :3], s["init"][:, 3:], s["book"]["t_init"], s["alpha"], s["events"])
-        filters.set_state(s["X"], s["P"])
-        self._state.upload(s["state"])
-        self._refs.upload(s["refs"])
-        self._book = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in s["book"].items()}
-        return self
+        out = self._after_launch(tj)
+        return out if tj.wanted else out[0]
 
 
-class PhoneSession:
+class PhoneSession(_ChunkedSession):
     """Live sessions from the phones' first message, fed as a server gets them: every chunk carries the next rows of
     the phase-2 plane and of the phase-3 plane (or the clients' wire frames), and costs two launches -- phase 2
     resumed (pekf_frontend_init_resume_dev), then phase 3 + the filter (pekf_live_join_dev) on phase 2's outputs
@@ -1025,37 +1065,31 @@ class PhoneSession:
     (FP64, AoS), as LiveSession's.  t_start (K,) int64: phase 2's start time (None: 0), with FP64 events only
     the t_init of a phone that never gets ready."""
 
-    def __init__(self, filters, n_avg=100, alpha=0.1, t_start=None):
-        if filters.layout != "aos" or filters.flags & RUN_MIXED_PRECISION:
-            raise ValueError("the fused front-end + filter kernel runs the FP64 filter on AoS state")
-        K = filters.batch
-        self.filters, self.batch, self.n_avg, self.alpha = filters, K, int(n_avg), float(alpha)
-        t0 = np.zeros(K, np.int64) if t_start is None else np.ascontiguousarray(t_start, np.int64).reshape(K)
-        self._alloc()
-        self._t_start.upload(t0)
-        check(lib.pekf_memset(self._state.ptr, 0, self._state.nbytes, None))   # no filter has joined
-        check(lib.pekf_device_sync())
-        self._book = dict(started=False, t_init=np.zeros(K, np.int64), dt_sum=np.zeros(K),
-                          total_counts=np.zeros(K, np.int64))
+    # (a snapshot carries both device states, phase 2's and the fused kernel's, and phase 2's latest outputs)
+    _BUFFERS = dict.fromkeys(("p2state", "state", "t_start", "init", "t_init", "ready", "refs"))
+    _FIELDS = ("n_avg", "alpha")
 
-    def _alloc(self):
+    def __init__(self, filters, n_avg=100, alpha=0.1, t_start=None):
+        super().__init__(filters)
         K = self.batch
+        self.n_avg, self.alpha = int(n_avg), float(alpha)
+        t0 = np.zeros(K, np.int64) if t_start is None else np.ascontiguousarray(t_start, np.int64).reshape(K)
         n2, n3 = int(lib.pekf_frontend_init_state_bytes(K, EV_F64_EVENTS)), int(lib.pekf_live_state_bytes(K, EV_F64_EVENTS))
         if n2 < 0 or n3 < 0:
             raise ValueError("no session state for FP64 events")
         self._p2state, self._state = DeviceBuffer(n2), DeviceBuffer(n3)
         self._t_start, self._init, self._t_init = DeviceBuffer(8 * K), DeviceBuffer(48 * K), DeviceBuffer(8 * K)
         self._ready, self._cnt, self._refs = DeviceBuffer(4 * K), DeviceBuffer(4 * K), DeviceBuffer(48 * K)
+        self._t_start.upload(t0)
+        check(lib.pekf_memset(self._state.ptr, 0, self._state.nbytes, None))   # no filter has joined
+        check(lib.pekf_device_sync())
 
-    total_counts = LiveSession.total_counts
-    _chunk_result = LiveSession._chunk_result
+    @classmethod
+    def _from_snapshot(cls, filters, s):
+        return cls(filters, s["n_avg"], s["alpha"])
 
-    @property
-    def refs(self):
-        """(K, 6) the filters' acc0 / mag0 as of the last chunk (NaN for a phone that is not ready)"""
-        if not self._book["started"]:
-            self._launch(None, 0, None, 0, False, None)
-        return self._refs.download((self.batch, 6), np.float64)
+    def _feed_no_rows(self):
+        self._launch(None, 0, None, 0, False, None)
 
     def _pack(self, ev, name):
         """A chunk's rows of one phase -> (DeviceBuffer or None, rows)"""
@@ -1086,11 +1120,9 @@ class PhoneSession:
         planes2 from byte offset2, n3 rows of planes3 from offset3 (offsets as LiveSession.feed_planes': inside the
         buffer, multiples of 16).  A buffer whose row count is 0 may be None.  calibration corrects the rows in
         place, so feed a row once."""
-        K = self.batch
         ptrs = []
         for planes, n, offset in ((planes2, int(n2), int(offset2)), (planes3, int(n3), int(offset3))):
-            if n < 0 or offset < 0 or offset % 16 or (n > 0 and (planes is None or offset + n * 32 * K > planes.nbytes)):
-                raise ValueError("offset / rows outside the planes buffer (or offset not a multiple of 16)")
+            self._rows_in(planes, n, offset, 32 * self.batch)
             ptrs.append(planes.ptr + offset if n else None)
         return self._launch(ptrs[0], int(n2), ptrs[1], int(n3), trajectory, calibration)
 
@@ -1112,7 +1144,7 @@ class PhoneSession:
                                 offset3=32 * self.batch * w["ev3_from"])
 
     def _launch(self, ev2, E2, ev3, E3, trajectory, calibration):
-        K, book, f = self.batch, self._book, self.filters
+        K, f = self.batch, self.filters
         if calibration is not None:
             if E2:
                 _apply_calibration(calibration, K, E2, ev2, EV_F64_EVENTS)
@@ -1120,52 +1152,20 @@ class PhoneSession:
                 _apply_calibration(calibration, K, E3, ev3, EV_F64_EVENTS)
         check(lib.pekf_frontend_init_resume_dev(K, E2, ev2, self._t_start.ptr, self.n_avg, self._init.ptr,
                                                 self._t_init.ptr, self._ready.ptr, EV_F64_EVENTS, self._p2state.ptr,
-                                                int(book["started"]), None))
+                                                int(self._book["started"]), None))
         tj = _Trajectory(chunk_trajectory_rows(trajectory, E3) if trajectory is True else trajectory, E3, K)
         # (no rows: any valid pointer, none is read)
         check(lib.pekf_live_join_dev(K, E3, ev3 if E3 else self._state.ptr, self._init.ptr, self._t_init.ptr,
                                      self.alpha, f.X.ptr, f.P.ptr, f.q, f.r, self._cnt.ptr, self._refs.ptr,
                                      EV_F64_EVENTS, self._state.ptr, tj.traj.ptr if tj.rows else None,
                                      tj.dt.ptr if tj.rows else None, tj.rows, None, None))
-        check(lib.pekf_device_sync())
-        book["started"] = True
-        counts = self._cnt.download((K,), np.int32)
-        ready = self._ready.download((K,), np.int32).astype(bool)
+        out = self._after_launch(tj)
+        return out[:1] + (self._ready.download((K,), np.int32).astype(bool),) + out[1:]
+
+    def _first_records(self, first):
         # a phone's record times start from the t_init of the chunk in which it applies its first record
-        first = (book["total_counts"] == 0) & (counts > 0)
         if first.any():
-            book["t_init"] = np.where(first, self._t_init.download((K,), np.int64), book["t_init"])
-        book["total_counts"] += counts
-        if not tj.wanted:
-            book["dt_sum"] = np.where(counts > 0, np.nan, book["dt_sum"])   # these records' dts were not asked for
-            return counts, ready
-        return counts, ready, self._chunk_result(tj.result(np.zeros(K)), counts)
-
-    _BUFFERS = ("p2state", "state", "t_start", "init", "t_init", "ready", "refs")
-
-    def snapshot(self):
-        """The session as host data, as LiveSession.snapshot: the bytes of both device states (phase 2's and the
-        fused kernel's), phase 2's latest outputs, X, P, refs and the host-side bookkeeping."""
-        X, P = self.filters.get_state()
-        snap = dict(batch=self.batch, n_avg=self.n_avg, alpha=self.alpha, q=self.filters.q, r=self.filters.r, X=X, P=P,
-                    book={k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in self._book.items()})
-        for name in self._BUFFERS:
-            buf = getattr(self, "_" + name)
-            snap[name] = buf.download((buf.nbytes,), np.uint8)
-        return snap
-
-    @classmethod
-    def restore(cls, filters, snapshot):
-        """A session that continues `snapshot` on `filters` (same batch, q and r), as LiveSession.restore."""
-        s = snapshot
-        if filters.batch != s["batch"] or (filters.q, filters.r) != (s["q"], s["r"]):
-            raise ValueError("restore needs a BatchedEKF of the snapshot's batch, q and r")
-        self = cls(filters, s["n_avg"], s["alpha"])
-        filters.set_state(s["X"], s["P"])
-        for name in cls._BUFFERS:
-            getattr(self, "_" + name).upload(s[name])
-        self._book = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in s["book"].items()}
-        return self
+            self._book["t_init"] = np.where(first, self._t_init.download((self.batch,), np.int64), self._book["t_init"])
 
 
 class FilterHandle:
