@@ -458,6 +458,32 @@ int pekf_magcal_dev(int64_t batch, int64_t n_events, const void *ev_planes, int 
  * status may be NULL (every phone calibrated). */
 int pekf_magcal_apply_dev(int64_t batch, int64_t n_events, void *ev_planes, const double *cal,
                           const int32_t *status, uint32_t flags, void *stream);
+/* Phase 1 fed in chunks: pekf_magcal_dev on the next n_events rows of the same phones' phase-1 plane, the way
+ * the server's Magnetometer_Calibration object takes one message at a time (setValues,
+ * KFS/Magnetometer_Calibration.cpp:13-43).  resume == 0 starts a session; resume != 0 continues it from `state`.
+ * What carries over, in `state`, is what that object holds (:7-36: x[100] y[100] z[100], bias, num_rows,
+ * isCalibrated): per phone the three running FP64 sums, the message count (it stops at n_cal + 1) and the first
+ * n_cal samples as doubles, which the fit reads a second time once the bias is known (:65-80).
+ *   cal, fit and status belong to the session: pass the same three buffers to every call.  The first call
+ * (resume == 0) writes every phone as not calibrated (status 1, bias 0, W = I, fit NaN).  A call rewrites a
+ * phone's outputs only if that phone's message n_cal + 1 is among its rows: then its fit runs (status 0, 2 or 3
+ * with pekf_magcal_dev's values).  A phone that has fired is never written again, and its later phase-1
+ * messages do nothing (:15: isCalibrated).  So after every call cal, fit and status are pekf_magcal_dev's on all
+ * the rows fed so far, bit for bit, however they were cut into calls.
+ *   n_cal MUST BE THE SAME in every call of a session (the state's size and layout depend on it; it is not
+ * checked).  state: a device buffer of pekf_magcal_state_bytes(batch, n_cal, flags) bytes, 16-byte aligned,
+ * required; its layout is private and belongs to one batch, its bytes may be copied.  flags and every other
+ * argument and check as pekf_magcal_dev; batch < 2^28.  fit may be NULL (then in every call).  The no-message /
+ * zero-step time events that pad a chunk move nothing.  n_events == 0 is legal and ev_planes may then be NULL:
+ * with resume == 0 it writes the outputs and the fresh state, otherwise it changes nothing. */
+int pekf_magcal_resume_dev(int64_t batch, int64_t n_events, const void *ev_planes, int n_cal, double *cal,
+                           double *fit, int32_t *status, uint32_t flags, void *state, int resume, void *stream);
+/* The bytes of a phase-1 session state for `batch` phones (host only): batch times a per-phone size that is a
+ * multiple of 16 -- the sums, the count and n_cal samples of 24 B, the arrays of
+ * KFS/Magnetometer_Calibration.cpp:7-12 as doubles.  < 0: a negative batch, n_cal outside [6, 2^30), or flags
+ * the call above refuses.  64 bits, spelled as pekf_live_state_bytes is. */
+long long
+int pekf_magcal_state_bytes(int64_t batch, int n_cal, uint32_t flags);
 
 /* The wire on the device: the clients' 100-byte frames (as MessageSender.java:217-233 sends and Server.cpp:35,84
  * receives them: "#<phase>,<type>:<x>,<y>,<z>,t:<ns>", spaces to 99 characters, '\n') -> FP64 event planes.

@@ -119,6 +119,8 @@ SIGNATURES = {
     "pekf_frontend_init_ext_dev": [_i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _u32, _vp],
     "pekf_magcal_dev": [_i64, _i64, _vp, _int, _vp, _vp, _vp, _u32, _vp],
     "pekf_magcal_apply_dev": [_i64, _i64, _vp, _vp, _vp, _u32, _vp],
+    "pekf_magcal_resume_dev": [_i64, _i64, _vp, _int, _vp, _vp, _vp, _u32, _vp, _int, _vp],
+    "pekf_magcal_state_bytes": [_i64, _int, _u32],
     "pekf_f32_wire_values": [_i64, _vp, _vp],
     "pekf_wire_parse": [ctypes.c_char_p, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64)],
     "pekf_wire_events_dev": [_i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -158,7 +160,7 @@ SIGNATURES = {
     "pekf_allreduce_max_dev": [_vp, _vp, _i64, _vp],
 }
 _RESTYPE = {"pekf_abi_version": ctypes.c_int, "pekf_last_error": ctypes.c_char_p, "pekf_live_state_bytes": _i64,
-            "pekf_frontend_init_state_bytes": _i64}
+            "pekf_frontend_init_state_bytes": _i64, "pekf_magcal_state_bytes": _i64}
 
 
 def _load():

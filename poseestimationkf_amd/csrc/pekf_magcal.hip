@@ -30,47 +30,20 @@
 // applying it to the raw samples before phase 3's interpolation (Parser.cpp:107's place) equals applying
 // it after (:239's place) in real arithmetic: phase 3 agrees with the reference's placement within
 // rounding, not bit for bit.
-#include "pekf_phase3.hpp"
+#include "pekf_magcal.hpp"
 
 namespace pekf {
 
-constexpr int kMcBlock = 256;
-constexpr bool kMcNtl = true;   // non-temporal event loads: every event is read once per pass (as phase 2's)
-constexpr int kMcRing = 8;         // event rows in flight per lane (k_frontend_init's)
-constexpr int kJacobiSweeps = 6;   // 3 x 3 symmetric: off-diagonal below 1e-15 of the norm after 6
 constexpr int kApplyRows = 64;     // k_magcal_apply: rows per lane at least (its 96 B of cal read once per chunk)
 // k_magcal_apply: rows in flight per lane, plain loads and 24 B stores.  Measured at 1,048,576 phones x 1,024 FP64
 // events (scripts/bench_magcal.py, interleaved twice): 12.0 ms; 8 rows in flight 12.1; whole 32 B events stored
 // 12.1; non-temporal loads 17.2 (the stores go to the lines just read).
 constexpr int kApplyRing = 4;
 
-// index of entry (i, j), i <= j, of a symmetric 6 x 6 held as its 21 upper entries
-__host__ __device__ constexpr int sym6(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
-
-// One Jacobi rotation of the symmetric 3 x 3 {a[p][p], a[q][q], a[p][q], a[r][p], a[r][q]} (r the third
-// index) and of the eigenvector columns p, q.  tau = (aqq - app) / (2 apq), t = the smaller root of
-// t^2 + 2 tau t - 1 = 0; a zero apq needs no rotation.
-__device__ __forceinline__ void jacobi_rot(double &app, double &aqq, double &apq, double &arp, double &arq,
-                                           double (&vp)[3], double (&vq)[3]) {
-#pragma clang fp contract(off)
-    if (apq == 0.0) return;
-    const double tau = (aqq - app) / (2.0 * apq);
-    const double t = __builtin_copysign(1.0, tau) / (fabs(tau) + sqrt(1.0 + tau * tau));
-    const double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
-    app = app - t * apq;
-    aqq = aqq + t * apq;
-    apq = 0.0;
-    const double rp = arp, rq = arq;
-    arp = c * rp - s * rq;
-    arq = s * rp + c * rq;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double kp = vp[k], kq = vq[k];
-        vp[k] = c * kp - s * kq;
-        vq[k] = s * kp + c * kq;
-    }
-}
-
+// (kMcBlock, kMcRing, kJacobiSweeps, sym6 and jacobi_rot: pekf_magcal.hpp, shared with k_magcal_resume.  Pass 2's
+// body and the solve below are stated a second time there, for that kernel: calling the shared statement from
+// here changed this kernel's register allocation and schedule, pekf_magcal.hpp says more.  Change one, change both;
+// tests/test_magcal_resume.py holds the two to the same bits.)
 template <bool EV64>
 __global__ __launch_bounds__(kMcBlock) void k_magcal(int64_t batch, int64_t n_events,
                                                      const std::conditional_t<EV64, double4, float4> *__restrict__ ev,

@@ -956,7 +956,7 @@ class _ChunkedSession:
             raise ValueError("restore needs a BatchedEKF of the snapshot's batch, q and r")
         self = cls._from_snapshot(filters, s)
         filters.set_state(s["X"], s["P"])
-        for name in cls._BUFFERS:
+        for name in self._BUFFERS:
             getattr(self, "_" + name).upload(s[name])
         self._book = copy.deepcopy(s["book"])
         return self
@@ -1047,6 +1047,75 @@ class LiveSession(_ChunkedSession):
         return out if tj.wanted else out[0]
 
 
+class CalibrationSession:
+    """Phase 1 fed in chunks (pekf_magcal_resume_dev): the phones' phase-1 messages as they arrive, a launch per
+    chunk; the running sums, the message counts and each phone's first n_cal samples stay on the device between
+    them (what the server's Magnetometer_Calibration object holds, KFS/Magnetometer_Calibration.cpp:7-36).
+
+    Any cutting of a phase-1 plane into chunks -- single rows, empty chunks, a phone's message n_cal + 1 as a
+    chunk's first or last row, phones that fire in different chunks or never -- gives
+    calibrate_magnetometer(all the rows, n_cal, events)'s cal, fit and status bit for bit, for every phone and
+    either event form, and after every chunk result() is that of the rows fed so far.  A phone's outputs are
+    written in the chunk that holds its message n_cal + 1 and never again: its later messages do nothing.
+
+    events: "f32" or "f64", fixed for the session; n_cal is fixed for the session too."""
+
+    def __init__(self, batch, n_cal=100, events="f32"):
+        if events not in EVENT_FORMS:
+            raise ValueError("events must be 'f32' or 'f64'")
+        K = self.batch = int(batch)
+        self.n_cal, self.events = int(n_cal), events
+        self._form = EV_F64_EVENTS if events == "f64" else 0
+        nbytes = int(lib.pekf_magcal_state_bytes(K, self.n_cal, self._form))
+        if nbytes < 0:
+            raise ValueError("no phase-1 session state for batch=%d, n_cal=%d (n_cal must be in [6, 2^30))" % (K, self.n_cal))
+        self._state, self._cal = DeviceBuffer(nbytes), DeviceBuffer(96 * K)
+        self._fit, self._status = DeviceBuffer(48 * K), DeviceBuffer(4 * K)
+        self.started = False
+        self._last_times = np.zeros(K, np.int64)
+
+    @property
+    def device(self):
+        """dict(cal, fit_dev, status_dev): the session's output buffers, what pekf_magcal_apply_dev reads"""
+        return dict(cal=self._cal, fit_dev=self._fit, status_dev=self._status)
+
+    def launch(self, ev_ptr, n_events, stream=None):
+        """pekf_magcal_resume_dev on n_events rows at the device address ev_ptr (None with no rows), enqueued"""
+        check(lib.pekf_magcal_resume_dev(self.batch, int(n_events), ev_ptr if n_events else None, self.n_cal,
+                                         self._cal.ptr, self._fit.ptr, self._status.ptr, self._form, self._state.ptr,
+                                         int(self.started), stream))
+        self.started = True
+
+    def feed(self, ev):
+        """The next rows of every phone's phase-1 stream: a synth.generate_calibration_events-style dict of types
+        (E, K), values (E, K, 3), times (E, K) and optionally values64; synth.EV_NONE where a phone has no message
+        in a row.  Every message is a sample, whatever its type."""
+        shape = np.asarray(ev["types"]).shape
+        if len(shape) != 2 or shape[1] != self.batch:
+            raise ValueError("phase1 is of %s phones, the session of %d" % (shape[1:], self.batch))
+        if shape[0] == 0:
+            return self.feed_planes(None, 0)
+        # (f32: the chunk's first gap from the previous chunk's last times; phase 1 reads no time)
+        buf, E, _ = _event_planes(dict(ev, t_init=self._last_times), self.events)
+        self._last_times = np.asarray(ev["times"], np.int64)[-1].copy()
+        return self.feed_planes(buf, E)
+
+    def feed_planes(self, planes, n_events, offset=0):
+        """n_events packed rows ([n_events][K] float4, or double4 for an FP64-event session) of the DeviceBuffer
+        `planes`, starting `offset` bytes into it: row ranges of one resident plane are fed without copies."""
+        n_events, offset = int(n_events), int(offset)
+        _ChunkedSession._rows_in(planes, n_events, offset, self.batch * (32 if self._form else 16))
+        self.launch(planes.ptr + offset if n_events else None, n_events)
+
+    def result(self):
+        """calibrate_magnetometer's dict (bias, W, fit, status, calibrated, cal, status_dev) from what has been
+        fed so far; cal / status_dev are the session's own buffers, which later chunks write."""
+        if not self.started:
+            self.launch(None, 0)
+        check(lib.pekf_device_sync())
+        return _calibration_result(self.batch, self.device)
+
+
 class PhoneSession(_ChunkedSession):
     """Live sessions from the phones' first message, fed as a server gets them: every chunk carries the next rows of
     the phase-2 plane and of the phase-3 plane (or the clients' wire frames), and costs two launches -- phase 2
@@ -1054,6 +1123,21 @@ class PhoneSession(_ChunkedSession):
     in device memory.  Phones do not move in lock-step: in one chunk some still average, some get ready, some
     already filter; each filter joins the fused session by itself, in the chunk that holds its first phase-3
     message once it is ready.
+
+    n_cal (None: no phase 1, the session above): the session calibrates from its own stream.  Every chunk may
+    also carry the next rows of the phones' phase-1 plane (phase1 / planes1; feed_frames takes them from the
+    frames), and the order within a chunk is: the phase-1 rows (pekf_magcal_resume_dev; always in the first
+    chunk, later only when the chunk has such rows), pekf_magcal_apply_dev on the chunk's phase-2 and phase-3
+    rows with the session's cal / status, phase 2 resumed, the join launch.  So a magnetometer message of
+    phases 2 / 3 is corrected with what is known once its own chunk's phase-1 rows are in, where the one-shot
+    session (run_session(..., calibration=calibrate_magnetometer(phase1, n_cal, events="f64")), for frames
+    run_wire_session(frames, filters, calibration="frames", n_cal=n_cal)) corrects every one.  The session equals
+    that one-shot bit for bit -- X, P, refs, ready, the summed counts, every trajectory row and record time, and
+    session.calibration -- for every phone that has no phase-2 or phase-3 magnetometer message in a chunk BEFORE
+    the chunk its fit fires in, and for every phone that never fires.  That is the client's own order: it
+    finishes its calibration stage first.  A phone outside it has the magnetometer messages of those earlier
+    chunks left as they came, which is what the server does (setValues and KFS/Parser.cpp:107 correct only once
+    isCalibrated is set) and where this session differs from the one-shot one.
 
     For every phone whose phase-2 messages all come before its phase-3 messages (the client's own order), any
     cutting of the rows into chunks gives run_session(phase2, phase3, filters, events="f64") -- for frames
@@ -1069,10 +1153,17 @@ class PhoneSession(_ChunkedSession):
     _BUFFERS = dict.fromkeys(("p2state", "state", "t_start", "init", "t_init", "ready", "refs"))
     _FIELDS = ("n_avg", "alpha")
 
-    def __init__(self, filters, n_avg=100, alpha=0.1, t_start=None):
+    def __init__(self, filters, n_avg=100, alpha=0.1, t_start=None, n_cal=None):
         super().__init__(filters)
         K = self.batch
         self.n_avg, self.alpha = int(n_avg), float(alpha)
+        self.n_cal = self._phase1 = None
+        if n_cal is not None:   # phase 1's state and outputs: the snapshot carries them, and n_cal
+            self.n_cal = int(n_cal)
+            self._phase1 = p1 = CalibrationSession(K, self.n_cal, "f64")
+            self._p1state, self._cal, self._fit, self._status = p1._state, p1._cal, p1._fit, p1._status
+            self._BUFFERS = dict(self._BUFFERS, **dict.fromkeys(("p1state", "cal", "fit", "status")))
+            self._FIELDS = self._FIELDS + ("n_cal",)
         t0 = np.zeros(K, np.int64) if t_start is None else np.ascontiguousarray(t_start, np.int64).reshape(K)
         n2, n3 = int(lib.pekf_frontend_init_state_bytes(K, EV_F64_EVENTS)), int(lib.pekf_live_state_bytes(K, EV_F64_EVENTS))
         if n2 < 0 or n3 < 0:
@@ -1086,10 +1177,28 @@ class PhoneSession(_ChunkedSession):
 
     @classmethod
     def _from_snapshot(cls, filters, s):
-        return cls(filters, s["n_avg"], s["alpha"])
+        return cls(filters, s["n_avg"], s["alpha"], n_cal=s.get("n_cal"))
 
     def _feed_no_rows(self):
         self._launch(None, 0, None, 0, False, None)
+
+    @property
+    def calibration(self):
+        """calibrate_magnetometer's dict as of the last chunk (a session with n_cal; otherwise None)"""
+        if self._phase1 is None:
+            return None
+        if not self._book["started"]:
+            self._feed_no_rows()
+        check(lib.pekf_device_sync())
+        return _calibration_result(self.batch, self._phase1.device)
+
+    def _check_phase1(self, calibration, has_phase1):
+        """The two refusals of a chunk's phase-1 arguments, before anything is packed or launched"""
+        if self._phase1 is not None and calibration is not None:
+            raise ValueError("a session constructed with n_cal calibrates from its own phase-1 rows: it takes no "
+                             "calibration=")
+        if self._phase1 is None and has_phase1:
+            raise ValueError("phase-1 rows need a calibrating session: construct the session with n_cal=")
 
     def _pack(self, ev, name):
         """A chunk's rows of one phase -> (DeviceBuffer or None, rows)"""
@@ -1103,48 +1212,70 @@ class PhoneSession(_ChunkedSession):
         planes = synth.pack_events64(ev, server_event_values(ev))
         return DeviceBuffer(planes.nbytes).upload(planes), shape[0]
 
-    def feed(self, phase2=None, phase3=None, trajectory=False, calibration=None):
+    def feed(self, phase2=None, phase3=None, trajectory=False, calibration=None, phase1=None):
         """The next rows of the phase-2 plane and of the phase-3 plane: each a dict of types (E, K), values
         (E, K, 3), times (E, K) and optionally values64, synth.EV_NONE where a phone has no message in a row;
         either may be None or have no rows, and the two need not have the same number.  calibration:
         calibrate_magnetometer's dict; both chunks are corrected on the device first (pekf_magcal_apply_dev: per
         event, so it needs no state).  Returns (counts (K,) int32 records applied in this chunk, ready (K,) bool
         phase 2's state after it), and with trajectory (True or a row cap) a third value, the dict of trajectory /
-        record_dt_ns / record_times_ns as LiveSession.feed's, rows counted within the chunk."""
+        record_dt_ns / record_times_ns as LiveSession.feed's, rows counted within the chunk.
+        phase1 (a session with n_cal only, which takes no calibration): the chunk's rows of the phase-1 plane, a
+        dict of the same form; every message in it is a calibration sample, whatever its type."""
+        self._check_phase1(calibration, phase1 is not None)
+        b1, E1 = self._pack(phase1, "phase1")
         b2, E2 = self._pack(phase2, "phase2")
         b3, E3 = self._pack(phase3, "phase3")
-        return self._launch(b2.ptr if E2 else None, E2, b3.ptr if E3 else None, E3, trajectory, calibration)
+        return self._launch(b2.ptr if E2 else None, E2, b3.ptr if E3 else None, E3, trajectory, calibration,
+                            b1.ptr if E1 else None, E1)
 
-    def feed_planes(self, planes2, n2, planes3, n3, trajectory=False, calibration=None, offset2=0, offset3=0):
+    def feed_planes(self, planes2, n2, planes3, n3, trajectory=False, calibration=None, offset2=0, offset3=0,
+                    planes1=None, n1=0, offset1=0):
         """Row ranges of resident FP64 event planes ([rows][K] double4 DeviceBuffers), without copies: n2 rows of
         planes2 from byte offset2, n3 rows of planes3 from offset3 (offsets as LiveSession.feed_planes': inside the
         buffer, multiples of 16).  A buffer whose row count is 0 may be None.  calibration corrects the rows in
-        place, so feed a row once."""
+        place, so feed a row once.  planes1 / n1 / offset1 (a session with n_cal only): the chunk's rows of the
+        phase-1 plane, in the same way; the session's own calibration corrects planes2 / planes3 in place too."""
+        self._check_phase1(calibration, planes1 is not None or int(n1) != 0)
         ptrs = []
-        for planes, n, offset in ((planes2, int(n2), int(offset2)), (planes3, int(n3), int(offset3))):
+        for planes, n, offset in ((planes2, int(n2), int(offset2)), (planes3, int(n3), int(offset3)),
+                                  (planes1, int(n1), int(offset1))):
             self._rows_in(planes, n, offset, 32 * self.batch)
             ptrs.append(planes.ptr + offset if n else None)
-        return self._launch(ptrs[0], int(n2), ptrs[1], int(n3), trajectory, calibration)
+        return self._launch(ptrs[0], int(n2), ptrs[1], int(n3), trajectory, calibration, ptrs[2], int(n1))
 
     def feed_frames(self, frames_chunk, calibration=None, trajectory=False):
         """The next [F][K][100] wire frames of the phones (wire.frames): parsed with a row per frame
         (wire_events(..., frame_rows=True): a frame's parse does not depend on earlier frames, and row f of each
         plane is frame f's message of that phase), then fed as feed_planes.  calibration: a dict, as feed;
-        "frames" is refused -- phase 1 is not chunked, calibrate first (calibrate_magnetometer)."""
-        if isinstance(calibration, str):
+        "frames" is refused -- without n_cal phase 1 is not chunked: calibrate first (calibrate_magnetometer), or
+        construct the session with n_cal=, which then parses the chunk's phase-1 messages too
+        (wire_events(..., phase1=True)) and feeds ev1's first E1 rows."""
+        if isinstance(calibration, str) and self._phase1 is None:
             raise ValueError("a chunked session takes calibrate_magnetometer's dict: phase 1 from the frames "
-                             "(calibration='frames') is not chunked")
+                             "(calibration='frames') is not chunked in this session -- construct the session with "
+                             "n_cal=")
+        self._check_phase1(calibration, False)
         F, Kf = _frames_shape(frames_chunk)
         if Kf != self.batch:
             raise ValueError("the frames are of %d phones, the session of %d" % (Kf, self.batch))
         if F == 0:
             return self._launch(None, 0, None, 0, trajectory, calibration)
+        if self._phase1 is not None:
+            w = wire_events(frames_chunk, None, True, phase1=True)
+            return self.feed_planes(w["ev2"], w["E2"], w["ev3"], w["E3"], trajectory, None,
+                                    offset3=32 * self.batch * w["ev3_from"], planes1=w["ev1"], n1=w["E1"])
         w = wire_events(frames_chunk, None, True)
         return self.feed_planes(w["ev2"], w["E2"], w["ev3"], w["E3"], trajectory, calibration,
                                 offset3=32 * self.batch * w["ev3_from"])
 
-    def _launch(self, ev2, E2, ev3, E3, trajectory, calibration):
+    def _launch(self, ev2, E2, ev3, E3, trajectory, calibration, ev1=None, E1=0):
         K, f = self.batch, self.filters
+        if self._phase1 is not None:   # the chunk's phase-1 rows first: its other rows are corrected with the result
+            if E1 or not self._book["started"]:
+                self._phase1.started = self._book["started"]   # (the book is what a snapshot carries)
+                self._phase1.launch(ev1, E1)
+            calibration = self._phase1.device
         if calibration is not None:
             if E2:
                 _apply_calibration(calibration, K, E2, ev2, EV_F64_EVENTS)
