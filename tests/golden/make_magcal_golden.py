@@ -26,7 +26,6 @@ from __future__ import annotations
 import importlib.util
 import os
 import sys
-from fractions import Fraction
 
 import numpy as np
 
@@ -39,25 +38,9 @@ sys.dont_write_bytecode = True
 os.environ.setdefault("MPLBACKEND", "Agg")
 
 from poseestimationkf_amd import synth  # noqa: E402
+from tests.magcal_numpy import exact_fit  # noqa: E402  (the exact rational solve, shared with the tests)
 
 K, N_CAL, SEED = 48, 100, 20240519
-
-
-def exact_fit(v):
-    """The exact solution of (A^T A) x = A^T 1 for the design rows of the float64 samples v (n, 3)."""
-    rows = []
-    for x, y, z in v:
-        x, y, z = Fraction(float(x)), Fraction(float(y)), Fraction(float(z))
-        rows.append([x * x, y * y, z * z, 2 * x * y, 2 * z * x, 2 * y * z])
-    M = [[sum(r[i] * r[j] for r in rows) for j in range(6)] + [sum(r[i] for r in rows)] for i in range(6)]
-    for c in range(6):  # Gauss-Jordan in rationals
-        p = next(r for r in range(c, 6) if M[r][c] != 0)
-        M[c], M[p] = M[p], M[c]
-        M[c] = [e / M[c][c] for e in M[c]]
-        for r in range(6):
-            if r != c and M[r][c] != 0:
-                M[r] = [a - M[r][c] * b for a, b in zip(M[r], M[c])]
-    return np.array([float(M[i][6]) for i in range(6)])
 
 
 def main():

@@ -156,6 +156,53 @@ def root_residual(W, R):
     return np.abs(W @ W - R).reshape(len(R), -1).max(axis=1) / np.abs(R).reshape(len(R), -1).max(axis=1)
 
 
+def eigh_root(R):
+    """R (K, 3, 3) symmetric positive definite -> NumPy's eigh-based principal root (V sqrt(lam)) V^T, the
+    yardstick of the fixture's w_ref."""
+    lam, V = np.linalg.eigh(R)
+    return (V * np.sqrt(lam)[:, None, :]) @ V.transpose(0, 2, 1)
+
+
+def scaled_root_residual(W, R):
+    """Per phone max_ij |V^T (W W - R) V|_ij / sqrt(lam_i lam_j) in R's own eigenbasis (NumPy's eigh): the
+    residual of each eigen-direction relative to that direction's eigenvalue, so an error along the small
+    eigenvalue is not hidden behind max|R| when kappa(R) is in the hundreds."""
+    lam, V = np.linalg.eigh(R)
+    E = V.transpose(0, 2, 1) @ (W @ W - R) @ V
+    return (np.abs(E) / np.sqrt(lam[:, :, None] * lam[:, None, :])).reshape(len(R), -1).max(axis=1)
+
+
+def exact_solve(v):
+    """The normal equations (A^T A) x = A^T 1 of the design rows [x^2, y^2, z^2, 2xy, 2zx, 2yz] of the float64
+    samples v (n, 3), formed and solved in rationals (fractions.Fraction, Gauss-Jordan): (x, pivots, exchanged)
+    -- the six unknowns and the six pivots as Fractions, and whether a row exchange was needed.  Without an
+    exchange pivot c is the ratio of the leading minors c + 1 and c, so A^T A is positive definite exactly when
+    exchanged is False and every pivot is > 0.  A singular system raises StopIteration."""
+    from fractions import Fraction
+    rows = []
+    for x, y, z in v:
+        x, y, z = Fraction(float(x)), Fraction(float(y)), Fraction(float(z))
+        rows.append([x * x, y * y, z * z, 2 * x * y, 2 * z * x, 2 * y * z])
+    M = [[sum(r[i] * r[j] for r in rows) for j in range(6)] + [sum(r[i] for r in rows)] for i in range(6)]
+    pivots, exchanged = [], False
+    for c in range(6):  # Gauss-Jordan in rationals
+        p = next(r for r in range(c, 6) if M[r][c] != 0)
+        exchanged = exchanged or p != c
+        M[c], M[p] = M[p], M[c]
+        pivots.append(M[c][c])
+        M[c] = [e / M[c][c] for e in M[c]]
+        for r in range(6):
+            if r != c and M[r][c] != 0:
+                M[r] = [a - M[r][c] * b for a, b in zip(M[r], M[c])]
+    return [M[i][6] for i in range(6)], pivots, exchanged
+
+
+def exact_fit(v):
+    """The exact solution of (A^T A) x = A^T 1 for the design rows of the float64 samples v (n, 3), rounded to
+    float64 at the end (tests/golden/magcal.npz's fit_exact)."""
+    return np.array([float(e) for e in exact_solve(v)[0]])
+
+
 def apply(values, types, bias, W, status=None):
     """W (m - bias) for the type-2 events of the calibrated phones: values (E, K, 3) float64 -> a corrected copy."""
     out = np.array(values, np.float64, copy=True)
