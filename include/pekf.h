@@ -485,6 +485,40 @@ int pekf_magcal_resume_dev(int64_t batch, int64_t n_events, const void *ev_plane
 long long
 int pekf_magcal_state_bytes(int64_t batch, int n_cal, uint32_t flags);
 
+/* A phone leaves, the next one starts afresh: one launch that returns the listed columns of a chunked session to
+ * the state a brand-new session gives them, every other column untouched.  It replaces what the reference does
+ * per connection: it serves one client per process (KFS/Server.cpp:58 accepts one, :93 ends on its disconnect), so
+ * its next phone gets a newly constructed Parser and its members (KFS/Parser.h:93 and the members around it:
+ * Magnetometer_Calibration -- KFS/Magnetometer_Calibration.cpp:7-12 --, the InitialValues, the KalmanFilter, the
+ * flags and counts).  A column recycled here and then fed a new phone's rows gives, bit for bit, what a new
+ * session fed those rows gives.
+ *   cols: n_cols DISTINCT column indices (device int32, any order; n_cols <= batch); one lane per listed column;
+ * an index outside [0, batch) writes nothing.  The session's buffers come as three optional groups: a group
+ * whose state pointer is NULL is not touched, a group given in part is PEKF_ERR_INVALID.
+ *   The filter (live_state, X, P, refs: pekf_live_join_dev's state / X / P / refs; flags must then be
+ * PEKF_EV_F64_EVENTS): the column's join mark is cleared (its 16 bytes of every plane of the state are zeroed),
+ * so the next pekf_live_join_dev starts it fresh from X / P; X[col] / P[col] (AoS) become X0[i] / P0[i] (device,
+ * [n_cols][4] / [n_cols][16], aligned with cols; both or neither) or, without them, pekf_reset_state_dev's
+ * [1,0,0,0] and I; refs[col] becomes NaN, a launch's refs for a phone that is not ready.  final_X / final_P
+ * (device, [n_cols][4] / [n_cols][16]; both or neither, only with this group): the column's X / P as they were,
+ * copied first -- the departing phone's last pose, without a download of every column.
+ *   Phase 2 (init_state, t_start, init, t_init, ready: pekf_frontend_init_resume_dev's): the state becomes what
+ * that call starts from with resume == 0 -- sums, counts and flags zero, both clocks at t_start_new[i] (device
+ * int64 [n_cols]; NULL: 0) -- t_start[col] the same time, and the outputs that call's for a phone with no rows:
+ * init NaN, t_init = the start time, ready 0.
+ *   Phase 1 (magcal_state, n_cal, cal, fit, status: pekf_magcal_resume_dev's; n_cal in [6, 2^30), the session's;
+ * fit is required here): sums and count zero, and the outputs "not calibrated" (status 1, bias 0, W = I, fit
+ * NaN), what that call writes for every phone with resume == 0.  The stored samples are left: a count of 0 makes
+ * every slot unread until it is rewritten.  This group does not depend on the event form.
+ *   batch < 2^28; the three state pointers 16-byte aligned.  n_cols == 0 or batch == 0: PEKF_OK, no launch.
+ * The sessions whose filters start from one launch-wide `resume` word (pekf_live_resume_dev) have no per-column
+ * fresh start and cannot be recycled. */
+int pekf_session_recycle_dev(int64_t batch, int64_t n_cols, const int32_t *cols, uint32_t flags, void *live_state,
+                             double *X, double *P, double *refs, const double *X0, const double *P0,
+                             double *final_X, double *final_P, void *init_state, int64_t *t_start, double *init,
+                             int64_t *t_init, int32_t *ready, const int64_t *t_start_new, void *magcal_state,
+                             int n_cal, double *cal, double *fit, int32_t *status, void *stream);
+
 /* The wire on the device: the clients' 100-byte frames (as MessageSender.java:217-233 sends and Server.cpp:35,84
  * receives them: "#<phase>,<type>:<x>,<y>,<z>,t:<ns>", spaces to 99 characters, '\n') -> FP64 event planes.
  * frames: [n_frames][batch][100] bytes (device; 4-byte aligned), phone b's frames in order along the first

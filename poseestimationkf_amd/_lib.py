@@ -138,6 +138,7 @@ SIGNATURES = {
                            _vp, _vp],
     "pekf_frontend_init_resume_dev": [_i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _u32, _vp, _int, _vp],
     "pekf_frontend_init_state_bytes": [_i64, _u32],
+    "pekf_session_recycle_dev": [_i64, _i64, _vp, _u32] + [_vp] * 8 + [_vp] * 6 + [_vp, _int, _vp, _vp, _vp] + [_vp],
     "pekf_log_scan": [ctypes.c_char_p, ctypes.POINTER(_i64)],
     "pekf_log_read": [ctypes.c_char_p, _i64, _vp, _vp, _vp, _vp, _dp, _dp, _dp],
     "pekf_log_read_ext": [ctypes.c_char_p, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64), _dp, _dp, _dp],

@@ -10,6 +10,9 @@
 // other registers, four more scalar instructions at the loop's exit; the row alone, shared, moved registers
 // too), so k_magcal stays as it was written and measured.  Change one statement, change the other: every test of
 // tests/test_magcal_resume.py compares the two kernels bit for bit.
+//
+// Last, MagcalState: the layout of k_magcal_resume's session state, which k_session_recycle
+// (pekf_session_recycle.hip) needs too, to write a column's fresh form.
 #pragma once
 #include "pekf_phase3.hpp"
 
@@ -145,5 +148,23 @@ __device__ __forceinline__ void magcal_solve_store(int64_t b, bool fired, double
     const int st = !fired ? 1 : !spd ? 2 : !ell ? 3 : 0;
     magcal_store(b, st, bx, by, bz, w, xs, cal, fit, status);
 }
+
+// The state of a session's phase 1, lane-minor planes as the other session states (pekf_phase3.hpp: state_plane):
+//   planes 0, 1 (16 B per lane each): {sum x, sum y}, {sum z, the message count in the low word};
+//   then 3 n_cal planes of 8 B per lane: component c of sample k of every phone is plane 3 k + c, so the phones
+//   that advance together store and load contiguous rows.
+// Per phone 32 + 24 n_cal bytes, rounded up to a multiple of 16 (an odd n_cal leaves 8 B unused).  Both event
+// forms keep doubles: (double)f of an f32 sample is exact.
+struct MagcalState {
+    static constexpr int kHeadPlanes = 2;
+    static __host__ __device__ constexpr int64_t bytes_per_phone(int n_cal) {
+        return 16 * kHeadPlanes + (((int64_t)24 * n_cal + 15) & ~(int64_t)15);
+    }
+    // component c of sample k of lane b.  One view of the buffer for stores and loads alike: pass 2 reads back
+    // what the same lane may have stored earlier in the same launch.
+    static __device__ __forceinline__ double *sample(void *state, int64_t batch, int64_t b, int k, int c) {
+        return reinterpret_cast<double *>(state_plane(state, batch, 0, kHeadPlanes)) + ((int64_t)(3 * (int64_t)k + c) * batch + b);
+    }
+};
 
 }  // namespace pekf

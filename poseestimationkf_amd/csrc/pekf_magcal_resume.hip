@@ -7,28 +7,11 @@
 // The sums alone do not do, as they do for chunked phase 2: the fit needs the n_cal samples a second time,
 // centred on a bias that is known only at message n_cal + 1 (setUncalibratedValues, :65-80), so the samples are
 // kept on the device.  When a phone's message n_cal + 1 arrives its lane fits from the store -- pass 2's body
-// and the solve are pekf_magcal.hpp's, k_magcal's own -- and writes its outputs once.
+// and the solve are pekf_magcal.hpp's, k_magcal's own -- and writes its outputs once.  The store's layout is
+// MagcalState (pekf_magcal.hpp).
 #include "pekf_magcal.hpp"
 
 namespace pekf {
-
-// The state of a session's phase 1, lane-minor planes as the other session states (pekf_phase3.hpp: state_plane):
-//   planes 0, 1 (16 B per lane each): {sum x, sum y}, {sum z, the message count in the low word};
-//   then 3 n_cal planes of 8 B per lane: component c of sample k of every phone is plane 3 k + c, so the phones
-//   that advance together store and load contiguous rows.
-// Per phone 32 + 24 n_cal bytes, rounded up to a multiple of 16 (an odd n_cal leaves 8 B unused).  Both event
-// forms keep doubles: (double)f of an f32 sample is exact.
-struct MagcalState {
-    static constexpr int kHeadPlanes = 2;
-    static __host__ __device__ constexpr int64_t bytes_per_phone(int n_cal) {
-        return 16 * kHeadPlanes + (((int64_t)24 * n_cal + 15) & ~(int64_t)15);
-    }
-    // component c of sample k of lane b.  One view of the buffer for stores and loads alike: pass 2 reads back
-    // what the same lane may have stored earlier in the same launch.
-    static __device__ __forceinline__ double *sample(void *state, int64_t batch, int64_t b, int k, int c) {
-        return reinterpret_cast<double *>(state_plane(state, batch, 0, kHeadPlanes)) + ((int64_t)(3 * (int64_t)k + c) * batch + b);
-    }
-};
 
 constexpr int kMcFitRing = 8;  // stored samples in flight per firing lane (pass 2)
 

@@ -1,7 +1,9 @@
 // pekf_phase2.hpp -- phase 2 of the server's Parser, what its two kernels share: k_frontend_init
 // (pekf_frontend.hip: one launch over a phone's whole phase-2 stream, means and variances) and
 // k_frontend_init_resume (pekf_frontend_resume.hip: the same stream fed in chunks, the means alone).  Their
-// block, ring depth and load form and the argument checks of their entries are stated here once.
+// block, ring depth and load form and the argument checks of their entries are stated here once.  So is InitState,
+// the chunked kernel's per-phone state between two launches: k_session_recycle (pekf_session_recycle.hip) writes
+// its fresh form for a column whose phone has left.
 //
 // Phase 2 (ProcessString, Parser.cpp:36-58; initialMeanAndCovariance, :84-140; InitialValues.cpp): the first
 // n_avg samples of each sensor type are averaged (a sequential FP64 sum divided by n_avg).  A sensor counts as
@@ -48,5 +50,48 @@ static inline int check_init_args(int64_t batch, int64_t n_events, int n_avg, ui
     PEKF_CHECK_ARG((uintptr_t)ev_planes % 16 == 0, "misaligned event planes");
     return PEKF_OK;
 }
+
+// What phase 2 holds for a phone between two rows (Parser::ProcessString's members, KFS/Parser.cpp:36-58):
+// the three sequential FP64 sums, the three sample counts, the three "initialised" flags, the "filter built"
+// flag and the two clocks (t: the f32 events' running clock; t_last: the time phase 3 starts from), in 7 planes
+// of 16 B per lane (pekf_phase3.hpp: state_plane).
+// Planes 0-3 the sums 0..7; 4 {sum 8, t}; 5 {t_last, cnt[0] | cnt[1] << 32}; 6 {cnt[2] | flags << 32, 0}: 112 B
+// per phone.  Read once before the event loop, written once after it.
+struct InitState {
+    static constexpr int kPlanes = 7;
+    static constexpr int kBytes = 16 * kPlanes;  // per phone
+
+    static __device__ __forceinline__ void load(void *state, int64_t batch, int64_t b, double (&sum)[3][3], int (&cnt)[3],
+                                                bool (&done)[3], bool &kalman, int64_t &t, int64_t &t_last) {
+        double2 v[kPlanes];
+#pragma unroll
+        for (int p = 0; p < kPlanes; ++p) v[p] = *state_plane(state, batch, b, p);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sum[i / 3][i % 3] = (i & 1) ? v[i / 2].y : v[i / 2].x;
+        sum[2][2] = v[4].x;
+        t = __double_as_longlong(v[4].y);
+        t_last = __double_as_longlong(v[5].x);
+        cnt[0] = __double2loint(v[5].y);
+        cnt[1] = __double2hiint(v[5].y);
+        cnt[2] = __double2loint(v[6].x);
+        const uint32_t flags = (uint32_t)__double2hiint(v[6].x);
+        done[0] = flags & 1u; done[1] = flags & 2u; done[2] = flags & 4u;
+        kalman = flags & 8u;
+    }
+    static __device__ __forceinline__ void store(void *state, int64_t batch, int64_t b, const double (&sum)[3][3],
+                                                 const int (&cnt)[3], const bool (&done)[3], bool kalman, int64_t t,
+                                                 int64_t t_last) {
+        const uint32_t flags = (done[0] ? 1u : 0u) | (done[1] ? 2u : 0u) | (done[2] ? 4u : 0u) | (kalman ? 8u : 0u);
+        const double2 v[kPlanes] = {make_double2(sum[0][0], sum[0][1]),
+                                    make_double2(sum[0][2], sum[1][0]),
+                                    make_double2(sum[1][1], sum[1][2]),
+                                    make_double2(sum[2][0], sum[2][1]),
+                                    make_double2(sum[2][2], __longlong_as_double(t)),
+                                    make_double2(__longlong_as_double(t_last), __hiloint2double(cnt[1], cnt[0])),
+                                    make_double2(__hiloint2double((int)flags, cnt[2]), 0.0)};
+#pragma unroll
+        for (int p = 0; p < kPlanes; ++p) *state_plane(state, batch, b, p) = v[p];
+    }
+};
 
 }  // namespace pekf

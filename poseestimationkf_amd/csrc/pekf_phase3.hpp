@@ -211,7 +211,8 @@ __device__ __forceinline__ void event_ring(const EvT *ev, int64_t batch, uint32_
     }
 }
 
-// A session's device state between two launches (LiveState, pekf_live.hpp; InitState, pekf_frontend_resume.hip):
+// A session's device state between two launches (LiveState, pekf_live.hpp; InitState, pekf_phase2.hpp; the header
+// planes of MagcalState, pekf_magcal.hpp):
 // lane-minor planes of 16 B per lane, [plane][batch], so a wave's load or store of a plane is one contiguous
 // 1 KB access.  Lane b's 16 bytes of plane p.
 __device__ __forceinline__ double2 *state_plane(void *state, int64_t batch, int64_t b, int p) {

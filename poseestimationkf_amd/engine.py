@@ -868,6 +868,32 @@ def chunk_trajectory_rows(trajectory, n_events):
     return (int(n_events) + 2) // 3 if trajectory is True else trajectory_rows(trajectory, n_events)
 
 
+def _recycle_columns(columns, batch):
+    """recycle's `columns` as (n,) int32 in the caller's order; refuses what is not a 1-D list of distinct
+    integer indices in [0, batch)"""
+    cols = np.asarray(columns)
+    if cols.size == 0 and cols.ndim == 1:
+        return np.zeros(0, np.int32)
+    if cols.ndim != 1 or not np.issubdtype(cols.dtype, np.integer):
+        raise ValueError("columns must be a 1-D sequence of integer column indices")
+    if cols.min() < 0 or cols.max() >= batch:
+        raise ValueError("columns must lie in [0, %d)" % batch)
+    if len(np.unique(cols)) != len(cols):
+        raise ValueError("columns lists a column twice")
+    return np.ascontiguousarray(cols, np.int32)
+
+
+def _launch_recycle(batch, cols, filter_group=None, phase2_group=None, phase1_group=None):
+    """pekf_session_recycle_dev on the host list cols, run to completion.  The groups are the entry's, as tuples
+    in its argument order with None for what is not given: (state, X, P, refs, X0, P0, final_X, final_P),
+    (state, t_start, init, t_init, ready, t_start_new), (state, n_cal, cal, fit, status)."""
+    dev = DeviceBuffer(4 * len(cols)).upload(cols)
+    f, p2, p1 = filter_group or (None,) * 8, phase2_group or (None,) * 6, phase1_group or (None, 0, None, None, None)
+    check(lib.pekf_session_recycle_dev(batch, len(cols), dev.ptr, EV_F64_EVENTS if filter_group else 0, *f, *p2, *p1,
+                                       None))
+    check(lib.pekf_device_sync())
+
+
 class _ChunkedSession:
     """A session fed in chunks, what LiveSession and PhoneSession share: the filters it refuses, the host
     bookkeeping (the summed counts, the running record times), what follows a chunk's launch, and snapshot /
@@ -972,7 +998,10 @@ class LiveSession(_ChunkedSession):
     the filters that applied a record in it; while the session runs they are outputs only (the session state
     holds the filter).  init_acc / init_mag (K, 3) host arrays of the raw phase-2 means, or init_acc a DeviceBuffer
     of phase 2's init (K, 6) and init_mag None (_launch_phase2's); t_init (K,) int64 host array or DeviceBuffer.
-    events: "f32" or "f64", fixed for the session (records are FP64 either way)."""
+    events: "f32" or "f64", fixed for the session (records are FP64 either way).
+
+    Its columns cannot be recycled (PhoneSession.recycle): every lane starts from the launch's one `resume` word,
+    so there is no per-lane fresh start; that needs the joining kernels on f32 events."""
 
     _BUFFERS, _FIELDS = dict(state=None, init=6, refs=6), ("events", "alpha")
 
@@ -1107,6 +1136,19 @@ class CalibrationSession:
         _ChunkedSession._rows_in(planes, n_events, offset, self.batch * (32 if self._form else 16))
         self.launch(planes.ptr + offset if n_events else None, n_events)
 
+    def recycle(self, columns):
+        """The phones of `columns` (distinct indices in [0, K), any order) leave and the next ones start afresh
+        (pekf_session_recycle_dev, its phase-1 group alone): sums and counts zero, outputs "not calibrated", as a
+        new session's; their stored samples are unread until rewritten.  Every other column is untouched.  Either
+        event form; an empty list launches nothing."""
+        cols = _recycle_columns(columns, self.batch)
+        if len(cols) == 0:
+            return
+        if not self.started:
+            self.launch(None, 0)
+        _launch_recycle(self.batch, cols, phase1_group=(self._state.ptr, self.n_cal, self._cal.ptr, self._fit.ptr,
+                                                        self._status.ptr))
+
     def result(self):
         """calibrate_magnetometer's dict (bias, W, fit, status, calibrated, cal, status_dev) from what has been
         fed so far; cal / status_dev are the session's own buffers, which later chunks write."""
@@ -1147,7 +1189,10 @@ class PhoneSession(_ChunkedSession):
 
     Sessions run on FP64 events (absolute times; pekf_live_join_dev takes nothing else).  filters: a BatchedEKF
     (FP64, AoS), as LiveSession's.  t_start (K,) int64: phase 2's start time (None: 0), with FP64 events only
-    the t_init of a phone that never gets ready."""
+    the t_init of a phone that never gets ready.
+
+    A phone that leaves frees its column: recycle(columns) returns the listed columns to a new session's state in
+    one launch, and the next phones' rows go into them while every other phone goes on."""
 
     # (a snapshot carries both device states, phase 2's and the fused kernel's, and phase 2's latest outputs)
     _BUFFERS = dict.fromkeys(("p2state", "state", "t_start", "init", "t_init", "ready", "refs"))
@@ -1297,6 +1342,59 @@ class PhoneSession(_ChunkedSession):
         # a phone's record times start from the t_init of the chunk in which it applies its first record
         if first.any():
             self._book["t_init"] = np.where(first, self._t_init.download((self.batch,), np.int64), self._book["t_init"])
+
+    def recycle(self, columns, t_start=None, X0=None, P0=None, final=False):
+        """The phones of `columns` leave and the next ones start afresh (pekf_session_recycle_dev, one launch): each
+        listed column returns to the state a brand-new session gives it -- calibration (a session with n_cal),
+        phase 2 and the filter -- and every other column goes on as if nothing had happened.  Fed a new phone's
+        rows, a recycled column equals, bit for bit, a new PhoneSession fed those rows; it is what the server does
+        per connection (one client per process, a new Parser for the next).  Valid at any chunk boundary, before
+        the first chunk included.
+
+        columns: a 1-D sequence of distinct integer indices in [0, K), in any order; an empty one launches nothing
+        and changes nothing.  t_start (n,) int64: the new phones' phase-2 start times, as the constructor's (None:
+        0).  X0 (n, 4) / P0 (n, 4, 4): the filters the new phones start from (both or neither; None: X = [1,0,0,0],
+        P = I, BatchedEKF.reset's).  final=True returns dict(X (n, 4), P (n, 4, 4), total_counts (n,)) of the
+        departing phones, in the order of `columns` -- their last poses from the same launch, not a download of
+        every column; otherwise None.  The columns' total_counts and record times start again.
+
+        LiveSession has no recycle: its lanes start from one launch-wide `resume` word, and a per-lane fresh start
+        there needs the joining kernels on f32 events, which do not exist."""
+        K = self.batch
+        cols = _recycle_columns(columns, K)
+        n = len(cols)
+        if (X0 is None) != (P0 is None):
+            raise ValueError("X0 needs P0 (and P0 needs X0)")
+        for name, a, shape in (("t_start", t_start, (n,)), ("X0", X0, (n, 4)), ("P0", P0, (n, 4, 4))):
+            if a is not None and np.shape(a) != shape:
+                raise ValueError("%s must have shape %s for %d columns" % (name, shape, n))
+        if n == 0:
+            return dict(X=np.zeros((0, 4)), P=np.zeros((0, 4, 4)), total_counts=np.zeros(0, np.int64)) if final else None
+        if not self._book["started"]:
+            self._feed_no_rows()   # the buffers in their started form (as refs does)
+        t0 = np.zeros(n, np.int64) if t_start is None else np.ascontiguousarray(t_start, np.int64)
+        # the entry's optional per-column arrays: X0, P0, final_X, final_P, t_start_new
+        bufs = [None if X0 is None else DeviceBuffer(32 * n).upload(f64(X0, (n, 4))),
+                None if P0 is None else DeviceBuffer(128 * n).upload(f64(P0, (n, 4, 4))),
+                DeviceBuffer(32 * n) if final else None, DeviceBuffer(128 * n) if final else None,
+                None if t_start is None else DeviceBuffer(8 * n).upload(t0)]
+        ptr = [b.ptr if b is not None else None for b in bufs]
+        f = self.filters
+        p1 = None
+        if self._phase1 is not None:
+            p1 = (self._p1state.ptr, self.n_cal, self._cal.ptr, self._fit.ptr, self._status.ptr)
+        _launch_recycle(K, cols, (self._state.ptr, f.X.ptr, f.P.ptr, self._refs.ptr) + tuple(ptr[:4]),
+                        (self._p2state.ptr, self._t_start.ptr, self._init.ptr, self._t_init.ptr, self._ready.ptr, ptr[4]),
+                        p1)
+        book = self._book
+        out = None
+        if final:
+            out = dict(X=bufs[2].download((n, 4), np.float64), P=bufs[3].download((n, 4, 4), np.float64),
+                       total_counts=book["total_counts"][cols].copy())
+        book["total_counts"][cols] = 0
+        book["dt_sum"][cols] = 0.0
+        book["t_init"][cols] = t0
+        return out
 
 
 class FilterHandle:
