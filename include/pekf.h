@@ -119,7 +119,9 @@ int pekf_comparator(int64_t n, const double *q1, const double *q2, double *out);
  * previousT bookkeeping (:62,:67), which stays with the caller: dt_ns = T - previousT.
  * gyro[n*3], dt_ns[n], X[n*4], P[n*16], Q[n*9], R[n*16] -> z[n*4], Pm[n*16], K[n*16].
  * Returns PEKF_ERR_SINGULAR if any S = Pm + R is singular (the reference raises
- * np.linalg.LinAlgError from np.linalg.inv, :65). */
+ * np.linalg.LinAlgError from np.linalg.inv, :65).  Singular means what it means to LAPACK: a
+ * pivot of the LU factorisation with partial pivoting is exactly zero.  No determinant is formed,
+ * so the scale of S does not matter, and K = Pm inv(S) carries an error of eps cond(S). */
 int pekf_predict(int64_t n, const double *gyro, const double *dt_ns, const double *X,
                  const double *P, const double *Q, const double *R, double *z, double *Pm,
                  double *K);

@@ -107,41 +107,65 @@ PEKF_DEV void rk4_literal(const double *q0, double dt_ns, const double *w, doubl
     for (int i = 0; i < 4; ++i) out[i] = out[i] / n;
 }
 
-// General 4x4 inverse by 2x2 cofactors (np.linalg.inv at ExtendedKalmanFilter.py:65).
-// Returns false iff the determinant is exactly zero (LinAlgError "Singular matrix").
+// x <-> y where sw, by selects on the values
+PEKF_DEV void swap_if(bool sw, double &x, double &y) {
+    const double t = sw ? y : x;
+    y = sw ? x : y;
+    x = t;
+}
+
+// General 4x4 inverse (np.linalg.inv at ExtendedKalmanFilter.py:65) as LAPACK forms it: LU with partial pivoting
+// (a -> U, one reciprocal per pivot as getf2 scales by it), b = inv(L) P formed beside it from the identity, then
+// U X = b by back substitution.  Its error is eps cond(S), where the 2x2-cofactor form it replaces lost eps cond^2
+// and, its determinant being a product of four entries, over- or underflowed on a well-conditioned S of entries
+// beyond 1e+-77 (tests/test_percall_conditioning.py; tests/percall_numpy.py restates both).  The residual S X - I is
+// the small one (a Gauss-Jordan sweep has the same forward error and a larger residual), which K = P- X = (S - R) X
+// needs.  No scaling: pivoting compares entries of one column only.
+// Row exchanges are compare-and-select on the values (the largest |a[r][c]|, r >= c, comes to row c): every index
+// is static, so a and b stay in registers (see pick4 in pekf_percall.hip).
+// Returns false iff a pivot is exactly zero after pivoting, LAPACK's own criterion for LinAlgError "Singular
+// matrix"; NaN/inf propagate.  inv is written either way (not meaningful when false).
 PEKF_DEV bool inverse4(const double *m, double *inv) {
-    const double s0 = m[0] * m[5] - m[4] * m[1];
-    const double s1 = m[0] * m[6] - m[4] * m[2];
-    const double s2 = m[0] * m[7] - m[4] * m[3];
-    const double s3 = m[1] * m[6] - m[5] * m[2];
-    const double s4 = m[1] * m[7] - m[5] * m[3];
-    const double s5 = m[2] * m[7] - m[6] * m[3];
-    const double c5 = m[10] * m[15] - m[14] * m[11];
-    const double c4 = m[9] * m[15] - m[13] * m[11];
-    const double c3 = m[9] * m[14] - m[13] * m[10];
-    const double c2 = m[8] * m[15] - m[12] * m[11];
-    const double c1 = m[8] * m[14] - m[12] * m[10];
-    const double c0 = m[8] * m[13] - m[12] * m[9];
-    const double det = s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
-    if (det == 0.0) return false;  // LAPACK raises only on an exactly singular pivot; NaN/inf propagate
-    const double id = 1.0 / det;
-    inv[0] = (m[5] * c5 - m[6] * c4 + m[7] * c3) * id;
-    inv[1] = (-m[1] * c5 + m[2] * c4 - m[3] * c3) * id;
-    inv[2] = (m[13] * s5 - m[14] * s4 + m[15] * s3) * id;
-    inv[3] = (-m[9] * s5 + m[10] * s4 - m[11] * s3) * id;
-    inv[4] = (-m[4] * c5 + m[6] * c2 - m[7] * c1) * id;
-    inv[5] = (m[0] * c5 - m[2] * c2 + m[3] * c1) * id;
-    inv[6] = (-m[12] * s5 + m[14] * s2 - m[15] * s1) * id;
-    inv[7] = (m[8] * s5 - m[10] * s2 + m[11] * s1) * id;
-    inv[8] = (m[4] * c4 - m[5] * c2 + m[7] * c0) * id;
-    inv[9] = (-m[0] * c4 + m[1] * c2 - m[3] * c0) * id;
-    inv[10] = (m[12] * s4 - m[13] * s2 + m[15] * s0) * id;
-    inv[11] = (-m[8] * s4 + m[9] * s2 - m[11] * s0) * id;
-    inv[12] = (-m[4] * c3 + m[5] * c1 - m[6] * c0) * id;
-    inv[13] = (m[0] * c3 - m[1] * c1 + m[2] * c0) * id;
-    inv[14] = (-m[12] * s3 + m[13] * s1 - m[14] * s0) * id;
-    inv[15] = (m[8] * s3 - m[9] * s1 + m[10] * s0) * id;
-    return true;
+    double a[4][4], b[4][4], rp[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            a[i][j] = m[4 * i + j];
+            b[i][j] = i == j ? 1.0 : 0.0;
+        }
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int r = c + 1; r < 4; ++r) {
+            const bool sw = fabs(a[r][c]) > fabs(a[c][c]);
+#pragma unroll
+            for (int j = c; j < 4; ++j) swap_if(sw, a[c][j], a[r][j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) swap_if(sw, b[c][j], b[r][j]);
+        }
+        ok &= a[c][c] != 0.0;
+        rp[c] = 1.0 / a[c][c];
+#pragma unroll
+        for (int r = c + 1; r < 4; ++r) {
+            const double l = a[r][c] * rp[c];
+#pragma unroll
+            for (int j = c + 1; j < 4; ++j) a[r][j] -= l * a[c][j];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[r][j] -= l * b[c][j];
+        }
+    }
+#pragma unroll
+    for (int r = 3; r >= 0; --r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            double s = b[r][j];
+#pragma unroll
+            for (int t = r + 1; t < 4; ++t) s -= a[r][t] * inv[4 * t + j];
+            inv[4 * r + j] = s * rp[r];
+        }
+    return ok;
 }
 
 // Wahba.RotationMatrix2Quart (Wahba.py:19-47): 3 branches, strict '>' ties, no trace branch.

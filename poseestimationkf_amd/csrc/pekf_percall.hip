@@ -416,7 +416,7 @@ __device__ __noinline__ void svc_run(uint32_t op, double *sh, int32_t *sh_status
 // entry (l / 4, l % 4) of each product with the source expression matmul<> uses for that entry (a
 // dot product from s = 0.0, the same contraction), so every entry rounds as on lane 0: the answers
 // stay bit-identical to the launch per call and to the batched kernels (tests/test_percall_service.py).
-// The parts with no product structure -- RK4, the cofactor inverse, the Wahba solve -- run on every
+// The parts with no product structure -- RK4, the pivoted inverse, the Wahba solve -- run on every
 // lane at once, which costs what they cost on one.  sx: LDS scratch shared through the wave.
 constexpr int kSvcScratch = 112;
 
@@ -480,7 +480,7 @@ __device__ __noinline__ void svc_predict_wave(double *sh, double *sx, int32_t *s
 #pragma unroll
     for (int k = 0; k < 16; ++k) S[k] = T[k];
     rk4_literal(x, dt, g, z);
-    const bool ok = inverse4(S, inv);  // inv is written only when ok
+    const bool ok = inverse4(S, inv);  // inv is meaningful only when ok
     if (lane == 0 && ok) {
 #pragma unroll
         for (int k = 0; k < 16; ++k) Si[k] = inv[k];

@@ -12,6 +12,12 @@ ill-conditioned in the reference's own arithmetic, within 10 x the disagreement 
 restatements of the reference (the C oracle and the NumPy one differ only in rounding); a Wahba
 quaternion also within 100 ulps of B's largest singular value over s2 + s3 (the SVD's own bound).
 
+A quarter of the items are ill conditioned: P = Q1 diag(10^(-k [0, 1/3, 2/3, 1])) Q2^T with k uniform in 0-8 (Q2 = Q1,
+symmetric, for half of them) and Q = q I, R = r I a thousandth of A P A^T's smallest singular value, so cond(S) is
+about 10^k.  There the gain is judged as tests/test_percall_conditioning.py judges it: against the exact rational
+P^- inv(S) of the device's own P^- (tests/percall_families.py), within 8 x the error of the reference's own
+np.linalg.inv statement on that item (or eps cond(S), where LAPACK happened to do better than that).
+
 usage: python3 scripts/fuzz_percall.py [--cases N] [--seed S]   (exit status 1 on any mismatch)
 """
 from __future__ import annotations
@@ -27,10 +33,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from oracle import ekf_numpy, oracle_c  # noqa: E402  (the checkers)
+from tests import percall_families as families  # noqa: E402  (the exact rational gain)
 from poseestimationkf_amd import engine  # noqa: E402
 
 TOL = 1e-12
 SPREAD = 10.0
+ILL = 0.25      # the fraction of ill-conditioned items
 
 
 def _unit(rng, shape):
@@ -54,6 +62,16 @@ def draw_case(rng):
     P = _spd(rng, n, 4, 0.0)
     P = np.where((rng.random(n) < 0.3)[:, None, None], P + rng.normal(scale=0.1, size=(n, 4, 4)), P)
     Q, R = _spd(rng, n, 3, 0.5), _spd(rng, n, 4, 0.5)
+    ill = rng.random(n) < ILL
+    if ill.any():
+        m = int(ill.sum())
+        k = rng.uniform(0.0, 8.0, size=m)
+        lam = 10.0 ** (-k[:, None] * np.array([0.0, 1.0 / 3.0, 2.0 / 3.0, 1.0]))
+        q1, q2 = np.linalg.qr(rng.normal(size=(m, 4, 4)))[0], np.linalg.qr(rng.normal(size=(m, 4, 4)))[0]
+        q2 = np.where((rng.random(m) < 0.5)[:, None, None], q1, q2)
+        P[ill] = (q1 * lam[:, None, :]) @ q2.transpose(0, 2, 1)
+        small = 1e-3 * 10.0 ** -k * np.sum(gyro[ill] ** 2, axis=1) / 4.0    # A P A^T = (|w|^2 / 4) (rotated P)
+        Q[ill], R[ill] = small[:, None, None] * np.eye(3), small[:, None, None] * np.eye(4)
     raw = rng.random() < 0.5
     sa, sm = (9.8, 45.0) if raw else (1.0, 1.0)
     acc = (_unit(rng, (n, 3)) + rng.normal(scale=0.05, size=(n, 3))) * sa
@@ -61,7 +79,20 @@ def draw_case(rng):
     acc0, mag0 = _unit(rng, (n, 3)) * sa, _unit(rng, (n, 3)) * sm
     ka = rng.uniform(-1.0, 2.0, size=n)
     return dict(n=n, gyro=gyro, dt=dt, X=X, P=P, Q=Q, R=R, acc=acc, mag=mag, acc0=acc0, mag0=mag0, ka=ka, km=1.0 - ka,
-                raw=raw)
+                raw=raw, ill=ill)
+
+
+def _gain_ok(Pm, K, Pn, Kn, R):
+    """An ill-conditioned item's K against the exact gain of the device's own P^-: (passes, its error, the bound)."""
+    S = Pm + R
+    exact = families.gain_exact(Pm, S)
+    if exact is None:
+        return False, np.inf, 0.0
+    e_lu = families.err(Kn, families.gain_exact(Pn, Pn + R))
+    sv = np.linalg.svd(S, compute_uv=False)
+    bound = max(families.MARGIN * e_lu, families.EPS * sv[0] / sv[-1])
+    e = families.err(K, exact)
+    return e <= bound, e, bound
 
 
 def _ok(err, ref, spread):
@@ -82,6 +113,11 @@ def check(c):
         for name, g, e in (("z", z[i], zn), ("P-", Pm[i], Pn), ("K", K[i], Kn), ("X", Xc[i], Xn), ("P", Pc[i], Pcn),
                            ("q_wahba", qw[i], qn)):
             err = np.abs(g - e)
+            if name == "K" and c["ill"][i]:
+                ok, e_k, bound = _gain_ok(Pm[i], K[i], Pn, Kn, c["R"][i])
+                if not ok:
+                    out.append("item %d K (ill conditioned): error %.3e against the exact gain, bound %.3e" % (i, e_k, bound))
+                continue
             if np.all(err <= TOL * np.maximum(1.0, np.abs(e))):
                 continue
             # the C restatement on the same inputs: how far the reference's own rounding moves this item
