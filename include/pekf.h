@@ -148,6 +148,15 @@ int pekf_wahba_rotation(int64_t n, const double *acc0, const double *mag0, const
 /* Wahba.getQuarternion(acc, mag, k_acc, k_mag), Wahba.py:49-50 -> q[n*4] */
 int pekf_wahba_quaternion(int64_t n, const double *acc0, const double *mag0, const double *acc,
                           const double *mag, const double *k_acc, const double *k_mag, double *q);
+/* The two on device pointers: the launch alone, on the caller's stream.  The result is the optimum wherever B is
+ * finite, whatever the vectors' lengths (each is brought to unit scale by an exact power of two); a pair counts
+ * as parallel (rank-1 B: the shortest arc) only where Gram-Schmidt's remainder is rounding noise, 2^-48 |mag|. */
+int pekf_wahba_rotation_dev(int64_t n, const double *acc0, const double *mag0, const double *acc,
+                            const double *mag, const double *k_acc, const double *k_mag, double *R,
+                            int32_t *status /* device int32[n]: 1 = B not finite; may be NULL */, void *stream);
+int pekf_wahba_quaternion_dev(int64_t n, const double *acc0, const double *mag0, const double *acc,
+                              const double *mag, const double *k_acc, const double *k_mag, double *q,
+                              int32_t *status /* as above */, void *stream);
 /* Wahba.RotationMatrix2Quart(M), Wahba.py:19-47 -> q[n*4] (3-branch, strict '>', no trace branch) */
 int pekf_rotmat_to_quat(int64_t n, const double *M, double *q);
 

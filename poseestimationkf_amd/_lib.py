@@ -89,6 +89,8 @@ SIGNATURES = {
     "pekf_correct_dev": [_i64] + [_vp] * 9 + [_vp],
     "pekf_wahba_rotation": [_i64] + [_vp] * 7,
     "pekf_wahba_quaternion": [_i64] + [_vp] * 7,
+    "pekf_wahba_rotation_dev": [_i64] + [_vp] * 7 + [_vp, _vp],
+    "pekf_wahba_quaternion_dev": [_i64] + [_vp] * 7 + [_vp, _vp],
     "pekf_rotmat_to_quat": [_i64, _vp, _vp],
     "pekf_run_dev": [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _u32, _vp],
     "pekf_run_rec64_dev": [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp],

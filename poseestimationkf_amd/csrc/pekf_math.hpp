@@ -371,11 +371,25 @@ PEKF_DEV bool wahba_b_finite(const double *acc0, const double *mag0, const doubl
     return ok;
 }
 
-// A frame whose pair does not span a plane to working accuracy: a zero vector (make_frame divides 0 by
-// 0: NaN), or m parallel to a, where Gram-Schmidt's remainder t = m - (m.e1) e1 is rounding noise and e2
-// = t/|t| is not orthogonal to e1 (|t| < 1e-12 |m|).  NaN inputs count as degenerate too.
+// A frame whose pair does not span a plane: a zero vector (make_frame divides 0 by 0: NaN), or m parallel to a,
+// where Gram-Schmidt's remainder t = m - (m.e1) e1 is rounding noise and e2 = t/|t| is not orthogonal to e1.  NaN
+// inputs count as degenerate too.  Noise means: no larger than rounding alone leaves of an exactly parallel pair.
+// With m = s a and u = 2^-53 the unit roundoff, to first order: e1_i = (a_i / |a|)(1 + d)(1 + eta_i), d the error
+// common to the three entries (a.a, a sum of positive terms: 3u; its root halves that and rounds: 2u; the
+// reciprocal: |d| <= 2.5u), eta_i <= 0.5u each product's own.  b1 = m.e1, again a sum of terms of one sign, adds
+// 3u to e1's, and b1 e1_i carries e1's error a second time and rounds once more: b1 e1_i = m_i (1 + 2d + 2 eta +
+// 3u + 0.5u), so |t| = |m - b1 e1| <= (5 + 1 + 3.5) u |m| ~ 10u |m| where every sign conspires, m's own rounding
+// (s a entry by entry, 0.5u) included; 7.5u is the most that a million random parallel pairs leave.
+// kDegenerateIeee = 32u = 2^-48 is three times the bound, and the thinnest pair that the reference's own SVD still
+// resolves to 1e-2, 1e-13 rad apart (|t| = 900u |m|), is 28 times above it.
+// FAST: |d| <= 4.2e-15 = 38u, the rsqrt's (above), and e1 is not renormalised, so t keeps 2 d beta1 <= 76u |m| of
+// an exactly parallel pair beside the 10u.  kDegenerateFast = 256u = 2^-45 is three times that, and 5e-13 rad
+// (4500u) is 17 times above it.
+constexpr double kDegenerateIeee = 0x1p-48, kDegenerateFast = 0x1p-45;
+template <int FAST = 0>
 PEKF_DEV bool frame_degenerate(const Frame &F) {
-    return !(F.beta2 * F.beta2 > 1e-24 * (F.beta1 * F.beta1 + F.beta2 * F.beta2)) || !(F.e1[0] == F.e1[0]);
+    constexpr double th = FAST ? kDegenerateFast : kDegenerateIeee;
+    return !(F.beta2 * F.beta2 > (th * th) * (F.beta1 * F.beta1 + F.beta2 * F.beta2)) || !(F.e1[0] == F.e1[0]);
 }
 
 // ---- Wahba with a rank-deficient B (Wahba.py:8-17) ----
@@ -493,13 +507,45 @@ PEKF_DEV void frame_pair(const Frame &F, double *a, double *m) {
     }
 }
 
+// v 2^-e, e the exponent that brings v's largest |entry| into [1/2, 1): an exact scaling (0 for a zero vector;
+// a non-finite one stays non-finite)
+PEKF_DEV int pow2_normalise(const double *v, double *o) {
+    int e;
+    (void)frexp(fmax(fmax(fabs(v[0]), fabs(v[1])), fabs(v[2])), &e);
+    o[0] = ldexp(v[0], -e); o[1] = ldexp(v[1], -e); o[2] = ldexp(v[2], -e);
+    return e;
+}
+
+// ka 2^ea and km 2^em with their common exponent removed: the larger of the two ends in [1/2, 1), the other
+// keeps its ratio to it (a zero weight stays out of the comparison; a ratio below 2^-1074 is 0, as it is to any
+// sum the two terms enter).
+PEKF_DEV void fold_weights(double &ka, int ea, double &km, int em) {
+    int xa, xm;
+    const double fa = frexp(ka, &xa), fm = frexp(km, &xm);
+    const int ta = fa != 0.0 ? xa + ea : -(1 << 20), tm = fm != 0.0 ? xm + em : -(1 << 20);
+    const int top = ta > tm ? ta : tm;
+    ka = ldexp(fa, max(ta - top, -1100));
+    km = ldexp(fm, max(tm - top, -1100));
+}
+
+// The per-call operators' solve (the IEEE route): the optimum wherever B is finite, whatever the four vectors'
+// lengths.  a.a overflows from |a| = 2^512 and is 0 from 2^-538 while B = ka acc0 acc^T + km mag0 mag^T may be
+// of order 1, so each vector is first brought to unit scale by an exact power of two.  The frames are those of
+// the unscaled vectors bit for bit; alpha, beta1, beta2 are theirs times 2^-e, and the optimum depends on the
+// two weighted terms ka aW aV, km (b1W, b2W) x (b1V, b2V) of (p, s) only through their ratio, so the four
+// exponents go into the weights (fold_weights).  Where nothing over- or underflowed before, every product is
+// the former one times a power of two and R is the same to the bit.
 PEKF_DEV void wahba_rotation_vectors(const double *acc0, const double *mag0, const double *acc,
                                      const double *mag, double ka, double km, double *R) {
+    double a0[3], m0[3], a[3], m[3];
+    const int ea = pow2_normalise(acc0, a0) + pow2_normalise(acc, a);
+    const int em = pow2_normalise(mag0, m0) + pow2_normalise(mag, m);
+    fold_weights(ka, ea, km, em);
     Frame W, V;
-    make_frame(acc0, mag0, W);
-    make_frame(acc, mag, V, wahba_sign(ka, km));
+    make_frame(a0, m0, W);
+    make_frame(a, m, V, wahba_sign(ka, km));
     if (frame_degenerate(W) || frame_degenerate(V))
-        wahba_rank1_rotation(acc0, mag0, acc, mag, ka, km, R);
+        wahba_rank1_rotation(a0, m0, a, m, ka, km, R);
     else
         wahba_rotation(W, V, ka, km, R);
 }

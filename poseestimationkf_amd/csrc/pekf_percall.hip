@@ -901,6 +901,18 @@ int pekf_wahba_quaternion(int64_t n, const double *acc0, const double *mag0, con
     return host_op<OpWahba<true>>(n, {{acc0, mag0, acc, mag, k_acc, k_mag}, {q}});
 }
 
+int pekf_wahba_rotation_dev(int64_t n, const double *acc0, const double *mag0, const double *acc,
+                            const double *mag, const double *k_acc, const double *k_mag, double *R,
+                            int32_t *status, void *stream) {
+    return dev_op<OpWahba<false>>(n, {{acc0, mag0, acc, mag, k_acc, k_mag}, {R}}, status, stream);
+}
+
+int pekf_wahba_quaternion_dev(int64_t n, const double *acc0, const double *mag0, const double *acc,
+                              const double *mag, const double *k_acc, const double *k_mag, double *q,
+                              int32_t *status, void *stream) {
+    return dev_op<OpWahba<true>>(n, {{acc0, mag0, acc, mag, k_acc, k_mag}, {q}}, status, stream);
+}
+
 int pekf_rotmat_to_quat(int64_t n, const double *M, double *q) { return host_op<OpR2q>(n, {{M}, {q}}); }
 
 }  // extern "C"

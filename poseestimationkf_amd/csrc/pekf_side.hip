@@ -171,7 +171,7 @@ __global__ __launch_bounds__(kSideBlock) void k_wahba_stream(int64_t batch, int6
             make_frame<true>(acc, mag, Vf, sg);
             double R9[9], y[4];
             wahba_rotation<true>(Wf, Vf, ka, km, R9);
-            if (frame_degenerate(Vf)) {  // a zero sample or acc parallel to mag: B has rank 1 (pekf_math.hpp)
+            if (frame_degenerate<1>(Vf)) {  // a zero sample or acc parallel to mag: B has rank 1 (pekf_math.hpp)
                 const double sa[3] = {a.x, a.y, a.z}, sm[3] = {a.w, m.x, m.y};  // from the record again
                 double a0[3], m0[3];
                 frame_pair(Wf, a0, m0);

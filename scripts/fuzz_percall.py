@@ -18,6 +18,13 @@ about 10^k.  There the gain is judged as tests/test_percall_conditioning.py judg
 P^- inv(S) of the device's own P^- (tests/percall_families.py), within 8 x the error of the reference's own
 np.linalg.inv statement on that item (or eps cond(S), where LAPACK happened to do better than that).
 
+An eighth of the items take their Wahba operands from the families of tests/wahba_families.py (pairs down to 1e-13
+rad, weights down to 1e-12, vectors times 2^+-520, optima beside the identity and a half turn), and are judged as
+tests/test_wahba_conditioning.py judges them: the quaternion against the exact one of tests/golden/wahba_families.npz,
+sign-insensitively, within 8 x the worst error of the reference's own statement on the item's family.  Those of the
+filter_weights family (whose weights are Correction's own |acc_z|, 1 - |acc_z|) are Correction's operands too, and X is
+held to z + K (y - z) normalised with the exact y, within that bound carried through K and the norm.
+
 usage: python3 scripts/fuzz_percall.py [--cases N] [--seed S]   (exit status 1 on any mismatch)
 """
 from __future__ import annotations
@@ -34,11 +41,13 @@ sys.path.insert(0, ROOT)
 
 from oracle import ekf_numpy, oracle_c  # noqa: E402  (the checkers)
 from tests import percall_families as families  # noqa: E402  (the exact rational gain)
+from tests import wahba_families  # noqa: E402  (the Wahba families and their exact optima)
 from poseestimationkf_amd import engine  # noqa: E402
 
 TOL = 1e-12
 SPREAD = 10.0
 ILL = 0.25      # the fraction of ill-conditioned items
+FAMILY = 0.125  # the fraction of items whose Wahba operands come from tests/wahba_families.py
 
 
 def _unit(rng, shape):
@@ -78,8 +87,40 @@ def draw_case(rng):
     mag = (_unit(rng, (n, 3)) + rng.normal(scale=0.05, size=(n, 3))) * sm
     acc0, mag0 = _unit(rng, (n, 3)) * sa, _unit(rng, (n, 3)) * sm
     ka = rng.uniform(-1.0, 2.0, size=n)
-    return dict(n=n, gyro=gyro, dt=dt, X=X, P=P, Q=Q, R=R, acc=acc, mag=mag, acc0=acc0, mag0=mag0, ka=ka, km=1.0 - ka,
-                raw=raw, ill=ill)
+    c = dict(n=n, gyro=gyro, dt=dt, X=X, P=P, Q=Q, R=R, acc=acc, mag=mag, acc0=acc0, mag0=mag0, ka=ka, km=1.0 - ka,
+             raw=raw, ill=ill)
+    # Wahba's own operands: the same samples, but for the items drawn from the families (fam: the item's row there)
+    fcat, rows = wahba_families.side_by_side(wahba_families.families())
+    fam = np.where(rng.random(n) < FAMILY, rng.integers(0, len(fcat["acc"]), n), -1)
+    w = {k: np.array(c[k]) for k in ("acc0", "mag0", "acc", "mag")}
+    hit = fam >= 0
+    for k in w:
+        w[k][hit] = fcat[k][fam[hit]]
+    c["ka"][hit], c["km"][hit] = fcat["k_acc"][fam[hit]], fcat["k_mag"][fam[hit]]
+    both = hit & (fam >= rows["filter_weights"].start) & (fam < rows["filter_weights"].stop)
+    for k in w:
+        c[k][both] = w[k][both]
+    c.update(w_acc0=w["acc0"], w_mag0=w["mag0"], w_acc=w["acc"], w_mag=w["mag"], fam=fam, both=both)
+    return c
+
+
+def _family_problems(c, i, q, X, z, K):
+    """A family item's q (and X, for filter_weights) by tests/test_wahba_conditioning.py's rule"""
+    g, j = wahba_families.golden(), c["fam"][i]
+    first = j - j % wahba_families.ITEMS
+    Yq = wahba_families.yard(g, "f64", slice(first, first + wahba_families.ITEMS))[1]
+    out = []
+    e = wahba_families.err_quat(q, g["f64_q"][j])[0]
+    if not e <= wahba_families.MARGIN * Yq:
+        out.append("item %d q_wahba (family row %d): error %.3e against the exact one, bound %.3e" % (i, j, e, 8 * Yq))
+    if c["both"][i]:
+        y = g["f64_q"][j] * (-1.0 if np.dot(g["f64_q"][j], z) < 0.0 else 1.0)
+        x = z + K @ (y - z)
+        bound = 2.0 * np.abs(K).sum(axis=1).max() * wahba_families.MARGIN * Yq / np.linalg.norm(x) + TOL
+        e = np.abs(X - x / np.linalg.norm(x)).max()
+        if not e <= bound:
+            out.append("item %d X (family row %d): error %.3e against the exact measurement, bound %.3e" % (i, j, e, bound))
+    return out
 
 
 def _gain_ok(Pm, K, Pn, Kn, R):
@@ -105,14 +146,18 @@ def check(c):
     out = []
     z, Pm, K = engine.predict(c["gyro"], c["dt"], c["X"], c["P"], c["Q"], c["R"])
     Xc, Pc = engine.correct(c["mag"], c["acc"], z, Pm, K, c["acc0"], c["mag0"])
-    qw = engine.wahba_quaternion(c["acc0"], c["mag0"], c["acc"], c["mag"], c["ka"], c["km"])
+    qw = engine.wahba_quaternion(c["w_acc0"], c["w_mag0"], c["w_acc"], c["w_mag"], c["ka"], c["km"])
     for i in range(c["n"]):
         zn, Pn, Kn = ekf_numpy.predict(c["gyro"][i], c["dt"][i], c["X"][i], c["P"][i], c["Q"][i], c["R"][i])
         Xn, Pcn = ekf_numpy.correct(c["mag"][i], c["acc"][i], z[i], Pm[i], K[i], c["acc0"][i], c["mag0"][i])
-        qn = ekf_numpy.wahba_quat(c["acc0"][i], c["mag0"][i], c["acc"][i], c["mag"][i], c["ka"][i], c["km"][i])
+        qn = ekf_numpy.wahba_quat(c["w_acc0"][i], c["w_mag0"][i], c["w_acc"][i], c["w_mag"][i], c["ka"][i], c["km"][i])
+        if c["fam"][i] >= 0:
+            out += _family_problems(c, i, qw[i], Xc[i], z[i], K[i])
         for name, g, e in (("z", z[i], zn), ("P-", Pm[i], Pn), ("K", K[i], Kn), ("X", Xc[i], Xn), ("P", Pc[i], Pcn),
                            ("q_wahba", qw[i], qn)):
             err = np.abs(g - e)
+            if c["fam"][i] >= 0 and (name == "q_wahba" or (name == "X" and c["both"][i])):
+                continue
             if name == "K" and c["ill"][i]:
                 ok, e_k, bound = _gain_ok(Pm[i], K[i], Pn, Kn, c["R"][i])
                 if not ok:
@@ -128,13 +173,13 @@ def check(c):
                 Xo, Po = oracle_c.correct(c["mag"][i], c["acc"][i], z[i], Pm[i], K[i], c["acc0"][i], c["mag0"][i])
                 alt = {"X": Xo, "P": Po}[name]
             else:
-                alt = oracle_c.wahba_quat(c["acc0"][i], c["mag0"][i], c["acc"][i], c["mag"][i], c["ka"][i], c["km"][i])
+                alt = oracle_c.wahba_quat(c["w_acc0"][i], c["w_mag0"][i], c["w_acc"][i], c["w_mag"][i], c["ka"][i], c["km"][i])
             spread = np.abs(alt - e)
             if name == "q_wahba":
                 # the rotation of an SVD moves by ~ |dB| / (s2 + s3) for a perturbation dB of B
                 # (LAPACK's error bound for the singular subspaces); the kernel's closed-form 3x3 SVD
                 # and the reference's gesdd round differently, so allow that bound at a few ulps of B
-                B = (c["ka"][i] * np.outer(c["acc0"][i], c["acc"][i]) + c["km"][i] * np.outer(c["mag0"][i], c["mag"][i]))
+                B = (c["ka"][i] * np.outer(c["w_acc0"][i], c["w_acc"][i]) + c["km"][i] * np.outer(c["w_mag0"][i], c["w_mag"][i]))
                 sv = np.linalg.svd(B, compute_uv=False)
                 spread = np.maximum(spread, 10 * np.finfo(float).eps * sv[0] / max(sv[1] + sv[2], 1e-300))
             if not _ok(err, e, spread):

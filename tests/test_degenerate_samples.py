@@ -9,7 +9,8 @@ arc (pekf_math.hpp: wahba_current_rank1 / wahba_rank1_rotation).  Both samples z
 as the reference does (its SVD returns the identity, and RotationMatrix2Quart divides 0 by 0 there).
 
 GPU: the per-call Wahba operators and the pure-Wahba side output attain the reference's optimum (a pair
-parallel to within 1e-12 counts as rank 1 there).  The fused kernels (multi-record, one-record, handle,
+counts as rank 1 there only where Gram-Schmidt's remainder is rounding noise, 2^-48 |mag| and 2^-45 |mag|;
+tests/test_wahba_conditioning.py holds pairs from 1e-13 rad apart to the exact rotation).  The fused kernels (multi-record, one-record, handle,
 the fused front-end + filter) detect a zero sample for free -- it makes their Wahba chain NaN, and the
 rare fallback branch, taken for NaN too, solves the rank-1 problem from the record re-read from memory
 -- and stay finite through such records.  An exactly parallel pair is not caught there (its Gram-Schmidt

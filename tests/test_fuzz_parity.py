@@ -5,7 +5,9 @@ random initial states, escaped dts and missing magnetometer samples.  The sweep 
 failure names a reproducible case; the GPU box runs longer sweeps of the same script
 (profiles/r3/fuzz/).  scripts/fuzz_live.py does the same for the fused front-end + filter kernel, which
 must equal the split pipeline bit for bit (and its records the front-end restatement's), and
-scripts/fuzz_percall.py the per-call operators item by item against the NumPy restatement."""
+scripts/fuzz_percall.py the per-call operators item by item against the NumPy restatement (a quarter of its gains
+against exact solves, tests/percall_families.py; an eighth of its Wahba items from tests/wahba_families.py against the
+exact optima of tests/golden/wahba_families.npz)."""
 from __future__ import annotations
 
 import importlib.util
