@@ -202,6 +202,30 @@ int pekf_run_ext_dev(int64_t batch, int64_t n_steps, int64_t window, int64_t ste
 int pekf_run_rec64_dev(int64_t batch, int64_t n_steps, int64_t window, int64_t step0, const void *plane_gd,
                        const void *plane_am, const void *plane_my, const double *refs, double *X, double *P,
                        double q, double r, double *traj, const int32_t *counts, void *stream);
+/* ---------------- per-filter noise: q and r per filter through the fused kernels ----------------
+ * The four entries below are pekf_run_ext_dev, pekf_run_rec64_dev, pekf_live_resume_dev and pekf_live_join_dev
+ * with `double q, double r` replaced by `const double *noise`: a plane double2 [batch] of {q, r} in device
+ * memory, 16-byte aligned, so filter b runs with Q = noise[2b] I and R = noise[2b + 1] I.  Each lane reads its
+ * entry once, before its first record (and its r once more at the launch's end); a filter whose entry is (q, r)
+ * gets, bit for bit, what the parent entry gives it with that q and r.  Every other argument, check and status is the parent's; a NULL or misaligned noise with
+ * batch > 0 is PEKF_ERR_INVALID before anything is launched.
+ *   Precondition, per entry of the plane: r finite and > 0, q finite and >= 0.  The entry cannot look at device
+ * memory, so it does not check this.  A filter whose entry breaks it gets NaN in its own X and P and no other
+ * filter is touched (nothing in the kernels indexes or loops on these values).
+ *   FP64 filter on AoS state only.  The one-record serving kernel, the filter handle (pekf_filter_*), the side
+ * outputs and pekf_live_dev / _ext_dev / _traj_dev take one q and one r for the launch. */
+/* pekf_run_ext_dev with per-filter noise (dt_ext may be NULL: pekf_run_dev).  flags must be 0:
+ * PEKF_RUN_MIXED_PRECISION and PEKF_RUN_STATE_SOA are refused (PEKF_ERR_INVALID).  Always the multi-record
+ * arithmetic, also for n_steps == 1 (as pekf_run_rec64_dev), so it equals pekf_run_ext_dev bit for bit for
+ * launches of n_steps >= 2. */
+int pekf_run_noise_dev(int64_t batch, int64_t n_steps, int64_t window, int64_t step0,
+                       const void *plane_gd, const void *plane_am, const void *plane_my, const double *dt_ext,
+                       const double *refs, double *X, double *P, const double *noise, double *traj,
+                       const int32_t *counts, uint32_t flags, void *stream);
+/* pekf_run_rec64_dev with per-filter noise. */
+int pekf_run_rec64_noise_dev(int64_t batch, int64_t n_steps, int64_t window, int64_t step0, const void *plane_gd,
+                             const void *plane_am, const void *plane_my, const double *refs, double *X, double *P,
+                             const double *noise, double *traj, const int32_t *counts, void *stream);
 /* AoS state (X[batch][4], P[batch][4][4]) <-> SoA state (X[4][batch], P[10][batch] holding
  * P00 P01 P02 P03 P11 P12 P13 P22 P23 P33).  to_soa != 0: AoS -> SoA, else SoA -> AoS. */
 int pekf_state_layout_dev(int64_t batch, double *X_aos, double *P_aos, double *X_soa, double *P_soa,
@@ -400,6 +424,20 @@ int pekf_live_join_dev(int64_t batch, int64_t n_events, const void *ev_planes, c
                        const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
                        int32_t *counts, double *refs, uint32_t flags, void *state, double *traj, double *traj_dt,
                        int64_t traj_rows, int *dev_error, void *stream);
+
+/* pekf_live_resume_dev and pekf_live_join_dev with per-filter noise (the plane `noise`, its precondition and what
+ * a filter that breaks it gets: see pekf_run_noise_dev above).  Like q and r in their parents, the plane must
+ * stay what it was for as long as a session lasts: the session state holds a filter's covariance in a form
+ * scaled by its r, so a changed r would reinterpret its P.  The one point at which a column's entry may change
+ * is pekf_session_recycle_dev, which starts that column's filter afresh: write the new phone's {q, r} before it. */
+int pekf_live_resume_noise_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                               const int64_t *t_init, double alpha, double *X, double *P, const double *noise,
+                               int32_t *counts, double *refs, uint32_t flags, void *state, int resume,
+                               double *traj, double *traj_dt, int64_t traj_rows, int *dev_error, void *stream);
+int pekf_live_join_noise_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                             const int64_t *t_init, double alpha, double *X, double *P, const double *noise,
+                             int32_t *counts, double *refs, uint32_t flags, void *state, double *traj,
+                             double *traj_dt, int64_t traj_rows, int *dev_error, void *stream);
 
 /* Phase 2 of the server's Parser (KFS/Parser.cpp:36-58,84-140; KFS/InitialValues.cpp) on the device: per
  * filter, the mean and sample variance of the first n_avg (the server: 100) samples of each sensor type,

@@ -341,10 +341,15 @@ struct LiveState {
 // t_init and X / P.  A lane is marked, and its state stored, at the end of a launch in which it was ready and
 // its column held a message; until then nothing of it is kept -- null rows move no state, so the fresh start at
 // the launch with its first message is the one launch that walked the null rows before it.
-template <bool TE, bool R64, bool EV64 = false, bool TRAJ = false, bool RESUME = false, bool JOIN = false>
+// NOISE (with RESUME; pekf_live_resume_noise.hip, pekf_live_join_noise.hip): per-filter noise, the lane's own q
+// and r from the {q, r} plane (NoiseQ, pekf_step.hpp) in place of the launch's.  The session state holds the
+// covariance as N, P = rI + sqrt(2) r D N D, so a lane's r must stay what it was for as long as its session lasts.
+template <bool TE, bool R64, bool EV64 = false, bool TRAJ = false, bool RESUME = false, bool JOIN = false,
+          bool NOISE = false>
 __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 ? PEKF_LIVE_EV64_WAVES : 2))) void k_live(
     int64_t batch, int64_t n_events, const std::conditional_t<EV64, double4, float4> *__restrict__ ev,
-    const double *__restrict__ init, const int64_t *__restrict__ t_init, double alpha, double qs, double rs,
+    const double *__restrict__ init, const int64_t *__restrict__ t_init, double alpha, NoiseQ<NOISE> q_arg,
+    NoiseR<NOISE> r_arg,
     double *__restrict__ Xio, double *__restrict__ Pio, int32_t *__restrict__ counts, double *__restrict__ refs,
     double *__restrict__ traj, double *__restrict__ traj_dt, int32_t traj_rows, void *__restrict__ state,
     int32_t resume) {
@@ -359,8 +364,11 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     // which is safe only while a block completes at most one record per lane
     static_assert(!R64 || kPush == 1, "SlotsLpf's single escaped-dt register needs one record per lane per block");
     static_assert(!JOIN || (RESUME && EV64), "lanes join a resumable session of FP64 events (absolute times)");
+    static_assert(!NOISE || (RESUME && (EV64 || R64)), "per-filter noise: the resumable and the joining kernels");
     const int64_t b = (int64_t)blockIdx.x * kRunBlock + threadIdx.x;
     if (b >= batch) return;
+    double qs, rs;
+    lane_noise(q_arg, r_arg, b, qs, rs);
 
     Phase3T<std::conditional_t<EV64, V3, F3>> fe;
     fe.start(init + 6 * b, t_init[b], alpha);
@@ -506,9 +514,9 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
             o[0] = make_double2(xo[0], xo[1]);
             o[1] = make_double2(xo[2], xo[3]);
         }
-        from_ref_basis(Wh, x, P, rs);
+        from_ref_basis(Wh, x, P, lane_r_again(q_arg, b, rs));
     } else {
-        from_ref_basis(Wr, x, P, rs);
+        from_ref_basis(Wr, x, P, lane_r_again(q_arg, b, rs));
     }
     store_state<false>(Xio, Pio, b, batch, x, P);
 }
@@ -529,6 +537,8 @@ struct LiveCall {
     double *traj, *traj_dt;  // read only when traj_rows > 0
     int64_t traj_rows;
     hipStream_t stream;
+    const double *noise = nullptr;  // the pekf_live_*_noise_dev entries: the {q, r} plane, in place of q and r
+    bool per_filter = false;        // ... and that the call is one of them
 };
 
 // The argument checks every pekf_live_* entry shares, in two halves: sizes, flags and the trajectory arguments
@@ -550,7 +560,11 @@ static inline int check_live_launch(const LiveCall &c) {
     PEKF_CHECK_ARG(c.n_events < ((int64_t)1 << 30), "n_events must be < 2^30 per launch");
     PEKF_CHECK_ARG(c.ev_planes && c.init && c.t_init && c.X && c.P && c.counts && c.refs, "null pointer");
     PEKF_CHECK_ARG((uintptr_t)c.ev_planes % 16 == 0, "misaligned event planes");
-    PEKF_CHECK_ARG(c.r > 0.0, "r must be > 0 (S = P- + rI must be SPD)");
+    if (c.per_filter)
+        PEKF_CHECK_ARG(c.noise && (uintptr_t)c.noise % 16 == 0,
+                       "noise must be a 16-byte aligned device pointer to batch {q, r} pairs");
+    else
+        PEKF_CHECK_ARG(c.r > 0.0, "r must be > 0 (S = P- + rI must be SPD)");
     return PEKF_OK;
 }
 
@@ -561,19 +575,32 @@ static inline int check_live_launch(const LiveCall &c) {
 //   <TRAJ, true>        a resumable launch takes FP64 records, so TE and the FP64-event form (pekf_live_resume.hip);
 //   <TRAJ, true, true>  filters join a session of FP64 events only (pekf_live_join.hip).
 // Without TRAJ the kernels read none of the trajectory arguments and are handed none.
-template <bool TRAJ, bool RESUME = false, bool JOIN = false>
+// NOISE: the same kernels' per-filter-noise forms (pekf_live_resume_noise.hip, pekf_live_join_noise.hip), handed
+// c.noise where the others are handed c.q and c.r.
+template <bool TRAJ, bool RESUME = false, bool JOIN = false, bool NOISE = false>
 int launch_k_live(const LiveCall &c, void *state = nullptr, int32_t resume = 0) {
+    static_assert(!NOISE || RESUME, "per-filter noise: the resumable and the joining kernels");
     const dim3 grid(grid_for(c.batch, kRunBlock)), block(kRunBlock);
+    NoiseQ<NOISE> q_arg;
+    NoiseR<NOISE> r_arg;
+    if constexpr (NOISE) {
+        q_arg = reinterpret_cast<const double2 *>(c.noise);
+    } else {
+        q_arg = c.q;
+        r_arg = c.r;
+    }
     auto launch = [&](auto kernel, const auto *ev) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, c.stream, c.batch, c.n_events, ev, c.init, c.t_init, c.alpha, c.q, c.r,
-                           c.X, c.P, c.counts, c.refs, TRAJ ? c.traj : nullptr, TRAJ ? c.traj_dt : nullptr,
+        hipLaunchKernelGGL(kernel, grid, block, 0, c.stream, c.batch, c.n_events, ev, c.init, c.t_init, c.alpha, q_arg,
+                           r_arg, c.X, c.P, c.counts, c.refs, TRAJ ? c.traj : nullptr, TRAJ ? c.traj_dt : nullptr,
                            TRAJ ? (int32_t)c.traj_rows : 0, state, resume);
     };
     if (JOIN || (c.flags & PEKF_EV_F64_EVENTS))  // the one FP64-event variant
-        launch(k_live<false, false, true, TRAJ, RESUME, JOIN>, static_cast<const double4 *>(c.ev_planes));
+        launch(k_live<false, false, true, TRAJ, RESUME, JOIN, NOISE>, static_cast<const double4 *>(c.ev_planes));
     else if constexpr (RESUME && !JOIN)
         dispatch_bools(
-            [&](auto te) { launch(k_live<te.value, true, false, TRAJ, true>, static_cast<const float4 *>(c.ev_planes)); },
+            [&](auto te) {
+                launch(k_live<te.value, true, false, TRAJ, true, false, NOISE>, static_cast<const float4 *>(c.ev_planes));
+            },
             (c.flags & PEKF_EV_TIME_EVENTS) != 0);
     else if constexpr (!RESUME)
         dispatch_bools(

@@ -278,6 +278,41 @@ __device__ __forceinline__ auto step_consts(double qs, double rs) {
     }
 }
 
+// Where the loop-form kernels (k_run, k_live) take Q = qI and R = rI from: a pair of kernel arguments, NoiseQ and
+// NoiseR.  Launch-wide (NOISE = false): the two doubles q and r.  Per filter (the kernels' NOISE form): a plane
+// double2 [batch] of {q, r} in device memory, 16-byte aligned, and nothing -- each lane reads its own entry once,
+// before the record loop, and everything derived from it (step_consts, the r of enter_ref_basis and
+// from_ref_basis) is the lane's own, written by the same expressions in the same order: a lane whose entry is
+// (q, r) rounds exactly as the launch-wide form with that q and r.  The fused algebra needs Q = qI and R = rI
+// per filter, not the same q and r in every lane.  (Two arguments in both forms, so that the launch-wide
+// kernels' argument block, and with it their code, is what it was.)
+struct NoNoiseArg {};
+template <bool NOISE>
+using NoiseQ = std::conditional_t<NOISE, const double2 *, double>;
+template <bool NOISE>
+using NoiseR = std::conditional_t<NOISE, NoNoiseArg, double>;
+// The precondition of a plane entry is r finite and > 0 (S = P- + rI must be SPD), q finite and >= 0, which no
+// host check can see in device memory: a lane whose entry breaks it takes NaN for both, so its own X and P
+// become NaN and nothing else happens (no index or trip count anywhere depends on these values).
+__device__ __forceinline__ void lane_noise(double q, double r, int64_t, double &qs, double &rs) {
+    qs = q;
+    rs = r;
+}
+__device__ __forceinline__ void lane_noise(const double2 *plane, NoNoiseArg, int64_t b, double &qs, double &rs) {
+    const double2 v = plane[b];
+    const bool ok = v.y > 0.0 && v.y < __builtin_inf() && v.x >= 0.0 && v.x < __builtin_inf();
+    qs = ok ? v.x : __builtin_nan("");
+    rs = ok ? v.y : __builtin_nan("");
+}
+// The lane's r again at a launch's end (from_ref_basis): re-read, not held through the record loop, where the
+// per-filter form then keeps three doubles of StepK (g2, r2, rp) and no more.  (volatile: a load the compiler
+// may not merge with lane_noise's.)
+__device__ __forceinline__ double lane_r_again(double, int64_t, double rs) { return rs; }
+__device__ __forceinline__ double lane_r_again(const double2 *plane, int64_t b, double) {
+    const double r = *reinterpret_cast<const volatile double *>(&plane[b].y);
+    return r > 0.0 && r < __builtin_inf() ? r : __builtin_nan("");
+}
+
 // Wahba-skip: no Correction for this record (X = z, P = P- = S - rI)
 template <bool LOOP>
 __device__ __forceinline__ void record_skip(double *x, const double *z, Sym4 &P, const Sym4 &S2, const StepK &k) {
@@ -583,22 +618,28 @@ __device__ __forceinline__ void from_ref_basis(const RW &Wr, double *x, Sym4T<PT
 // T - previousT the reference accepts (ExtendedKalmanFilter.py:62).  A separate instantiation, so the
 // windows without escapes (every synthetic and front-end stream but the rare long pause) pay nothing.
 // HOIST: the Correction's state-independent half ahead of the missing branch (ekf_record_step).
+// NOISE: per-filter noise (NoiseQ / NoiseR above; pekf_run_noise.hip instantiates these kernels): the lane's own
+// q and r in place of the launch's, FP64 on AoS state.
 template <typename R, bool TRAJ, bool MIXED, bool SOA, bool COUNTS, bool PIN = false, bool LONGDT = false,
-          bool HOIST = false>
+          bool HOIST = false, bool NOISE = false>
 __global__ __launch_bounds__(kRunBlock) PEKF_RUN_ATTR void k_run(int64_t batch, int64_t n_steps, int64_t window,
                                                    int64_t step0, const decltype(R::gd) *__restrict__ gd,
                                                    const decltype(R::gd) *__restrict__ am,
                                                    const decltype(R::my) *__restrict__ my,
                                                    const double *__restrict__ refs,
                                                    double *__restrict__ Xio, double *__restrict__ Pio,
-                                                   double qs, double rs, double *__restrict__ traj,
+                                                   NoiseQ<NOISE> q_arg, NoiseR<NOISE> r_arg,
+                                                   double *__restrict__ traj,
                                                    const int32_t *__restrict__ counts,
                                                    const double *__restrict__ dtx) {
     using PT = typename std::conditional<MIXED, float, double>::type;
     constexpr bool kRec64 = std::is_same<R, Rec64>::value;
     static_assert(!(kRec64 && LONGDT), "an FP64 record's dt is the float64 itself: no side plane");
+    static_assert(!NOISE || !(MIXED || SOA || HOIST), "per-filter noise: FP64, AoS state, no HOIST");
     const int64_t b = (int64_t)blockIdx.x * kRunBlock + threadIdx.x;
     if (b >= batch) return;
+    double qs, rs;
+    lane_noise(q_arg, r_arg, b, qs, rs);
     const int32_t my_steps = COUNTS ? (counts[b] < n_steps ? counts[b] : (int32_t)n_steps) : (int32_t)n_steps;
 
     // per-filter constants: the Wahba reference frame of (acc0, mag0) (Wahba.py:4-6)
@@ -686,7 +727,7 @@ __global__ __launch_bounds__(kRunBlock) PEKF_RUN_ATTR void k_run(int64_t batch, 
     }
     if constexpr (!MIXED) mode.leave();
     if (COUNTS && my_steps == 0) return;
-    from_ref_basis(Wr, x, P, rs);
+    from_ref_basis(Wr, x, P, lane_r_again(q_arg, b, rs));
     store_state<SOA>(Xio, Pio, b, batch, x, P);
 }
 

@@ -535,6 +535,14 @@ class _Trajectory:
         return dict(trajectory=tr, record_dt_ns=dt, record_times_ns=record_times_ns(t_init, dt))
 
 
+def _scalar_noise_only(filters, what, session):
+    """Refuses a per-filter-noise filter in a one-launch session, naming the chunked session to feed instead"""
+    if getattr(filters, "noise", None) is not None:
+        raise ValueError("%s runs the one-launch live kernels, which take one q and one r for the batch: feed a "
+                         "per-filter-noise BatchedEKF through %s instead (one chunk gives the same launch)"
+                         % (what, session))
+
+
 def _run_live(filters, ev_planes, n_events, init, t_init, alpha, flags, trajectory, stream=None):
     """The fused launch every session ends in, run to completion: filters.run_events_async on device event
     planes and phase-2 results, with the trajectory buffers `trajectory` asks for -> (counts, refs DeviceBuffers,
@@ -583,6 +591,7 @@ def run_session(phase2, phase3, filters, n_avg=100, alpha=0.1, records="f64", ev
     after its own r-th record, the server's X_k --, record_dt_ns (R, K) the dt it was applied with and
     record_times_ns (R, K) its time (record_times_ns()); NaN from row counts[k] on."""
     K = filters.batch
+    _scalar_noise_only(filters, "run_session", "PhoneSession")
     assert np.asarray(phase2["types"]).shape[1] == K and np.asarray(phase2["types"]).shape[0] > 0
     assert np.asarray(phase3["types"]).shape[1] == K
     t_last = np.asarray(phase2["times"], np.int64)[-1]
@@ -683,6 +692,7 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     Raises ValueError, before anything is launched, if
     filters.batch is not the frames' phone count or calibration is another string."""
     K = filters.batch
+    _scalar_noise_only(filters, "run_wire_session", "PhoneSession (feed_frames)")
     from_frames = isinstance(calibration, str)
     if from_frames and calibration != "frames":
         raise ValueError("calibration must be None, calibrate_magnetometer's dict or 'frames'")
@@ -722,29 +732,97 @@ def _launch_counts(win, counts, n_steps, step0):
     return DeviceBuffer(c.nbytes).upload(c)
 
 
+def _noise_arrays(q, r, n, what="batch"):
+    """q and r, each a scalar or an array-like of n values, as two (n,) float64 arrays; refuses, on the host, a
+    wrong shape, a non-finite value, r <= 0 and q < 0 (the device entries' precondition, include/pekf.h)."""
+    out = []
+    for name, v in (("q", q), ("r", r)):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape != (n,)):
+            raise ValueError("%s must be a scalar or %d values (one per %s), not of shape %s" % (name, n, what, a.shape))
+        a = np.array(np.broadcast_to(a, (n,)))   # (a copy: the filter's own arrays)
+        if not np.isfinite(a).all():
+            raise ValueError("every %s must be finite" % name)
+        out.append(a)
+    if (out[1] <= 0).any():
+        raise ValueError("every r must be > 0 (S = P- + rI must be SPD)")
+    if (out[0] < 0).any():
+        raise ValueError("every q must be >= 0")
+    return out[0], out[1]
+
+
 class BatchedEKF:
     """B independent filters of the reference model, state resident on the device.
 
     Equivalent, filter by filter, to the reference's main_file.py:19-47 driver:
     KalmanFilter(T0, mag_0, acc_0) with setQ(q), setR(r), P = I, X = [1,0,0,0], then
     Prediction + Correction for every record.  `run` advances all filters n_steps records.
+
+    Noise, launch-wide or per filter.  Two scalars q and r: one Q = qI and R = rI for the whole batch, kernel
+    arguments of every launch (self.noise is None).  If either is an array-like of `batch` values, the filter has
+    per-filter noise: self.q and self.r are (batch,) float64 arrays and self.noise is a DeviceBuffer of 16 B per
+    filter, {q, r}, which run / run_async (all three window kinds), LiveSession and PhoneSession hand to the
+    per-filter-noise kernels (pekf_*_noise_dev); a filter whose pair is (q, r) gets the scalar launch's bits.
+    self.noise is written by the constructor, by set_noise -- for the run paths, where P is stored plain between
+    launches -- and by PhoneSession.recycle(q=, r=).  Recycling is the only point at which a live session
+    column's noise may change: the session state holds the covariance in an r-scaled form (N, with P = rI +
+    sqrt(2) r D N D), so changing a column's r in mid-session would reinterpret its P.
+    Scalar-only: FilterHandle, the drop-ins, the one-record online path (a per-filter launch of one record runs
+    the multi-record arithmetic), the side-output kernels, precision="mixed", layout="soa" and
+    shard.MultiDeviceEKF.
     """
 
     def __init__(self, batch, q=1.0, r=0.1, precision="f64", layout="aos"):
         """precision: "f64" (default, as the reference) or "mixed" (covariance path in f32).
         layout: "aos" (X[B][4], P[B][4][4]) or "soa" (X[4][B], P[10][B]: coalesced state access,
-        for launches that cover few records, e.g. online serving)."""
+        for launches that cover few records, e.g. online serving).
+        q, r: each a scalar or an array-like of batch values (per-filter noise: FP64 on AoS state only)."""
         if precision not in ("f64", "mixed"):
             raise ValueError("precision must be 'f64' or 'mixed'")
         if layout not in ("aos", "soa"):
             raise ValueError("layout must be 'aos' or 'soa'")
         self.batch = int(batch)
-        self.q, self.r = float(q), float(r)
+        self.noise = None
+        if np.ndim(q) == 0 and np.ndim(r) == 0:
+            self.q, self.r = float(q), float(r)
+        else:   # validated on the host, before any device call
+            if precision != "f64" or layout != "aos":
+                raise ValueError("per-filter noise (array q / r) runs the FP64 filter on AoS state: not with "
+                                 "precision='mixed' or layout='soa'")
+            self.q, self.r = _noise_arrays(q, r, self.batch)
+            self.noise = DeviceBuffer(16 * self.batch).upload(np.stack([self.q, self.r], axis=1))
         self.layout = layout
         self.flags = _run_flags(precision, layout)
         self.X = DeviceBuffer(32 * self.batch)
         self.P = DeviceBuffer((80 if layout == "soa" else 128) * self.batch)
         self.reset()
+
+    @property
+    def per_filter_noise(self):
+        """True if q and r are per filter (self.noise holds them on the device)"""
+        return self.noise is not None
+
+    def same_noise(self, q, r):
+        """True if this filter's q and r equal the given ones (scalars or arrays), as restore needs them"""
+        return (np.ndim(q) == np.ndim(self.q) and np.ndim(r) == np.ndim(self.r) and
+                np.array_equal(self.q, q) and np.array_equal(self.r, r))
+
+    def set_noise(self, columns, q, r):
+        """New noise for the listed columns of a per-filter-noise filter: q and r scalars or one value per listed
+        column, validated as the constructor's, written to self.q / self.r and to those entries of self.noise
+        (synchronous).  For the run paths, where P is stored plain between launches; a live session's column may
+        change its noise only when it is recycled (PhoneSession.recycle(q=, r=), which calls this)."""
+        if self.noise is None:
+            raise ValueError("set_noise needs a per-filter-noise filter: construct BatchedEKF with array q / r")
+        cols = _recycle_columns(columns, self.batch)
+        qn, rn = _noise_arrays(q, r, len(cols), "listed column")
+        if len(cols) == 0:
+            return
+        self.q[cols], self.r[cols] = qn, rn
+        lo, hi = int(cols.min()), int(cols.max()) + 1   # one copy of the range that holds them
+        part = np.ascontiguousarray(np.stack([self.q[lo:hi], self.r[lo:hi]], axis=1))
+        check(lib.pekf_memcpy_h2d(self.noise.ptr + 16 * lo, part.ctypes.data, part.nbytes, None))
+        check(lib.pekf_device_sync())
 
     def _to_layout(self, Xa, Pa, to_soa, stream=None):
         check(lib.pekf_state_layout_dev(self.batch, Xa.ptr, Pa.ptr, self.X.ptr, self.P.ptr, int(to_soa), stream))
@@ -783,10 +861,20 @@ class BatchedEKF:
         """Enqueue one fused launch; traj: optional DeviceBuffer of n_steps*batch*32 bytes;
         counts: optional DeviceBuffer of batch int32 (filter b applies its first counts[b] records).
         A window with a dt side plane (escaped records) runs pekf_run_ext_dev with it; a RecordWindow64
-        (FP64 records) runs pekf_run_rec64_dev."""
+        (FP64 records) runs pekf_run_rec64_dev.  A per-filter-noise filter runs their pekf_run_noise_dev /
+        pekf_run_rec64_noise_dev (always the multi-record arithmetic, also for one record)."""
         assert win.batch == self.batch
         tr, cn = traj.ptr if traj is not None else None, counts.ptr if counts is not None else None
-        if isinstance(win, RecordWindow64):
+        if self.noise is not None:
+            if isinstance(win, RecordWindow64):
+                check(lib.pekf_run_rec64_noise_dev(self.batch, int(n_steps), win.window, int(step0), win.gd.ptr,
+                                                   win.am.ptr, win.my.ptr, win.refs.ptr, self.X.ptr, self.P.ptr,
+                                                   self.noise.ptr, tr, cn, stream))
+            else:
+                check(lib.pekf_run_noise_dev(self.batch, int(n_steps), win.window, int(step0), win.gd.ptr, win.am.ptr,
+                                             win.my.ptr, win.dtx.ptr if win.dtx is not None else None, win.refs.ptr,
+                                             self.X.ptr, self.P.ptr, self.noise.ptr, tr, cn, self.flags, stream))
+        elif isinstance(win, RecordWindow64):
             if self.layout != "aos" or self.flags & RUN_MIXED_PRECISION:
                 raise ValueError("FP64-record windows run the FP64 filter on AoS state")
             check(lib.pekf_run_rec64_dev(self.batch, int(n_steps), win.window, int(step0), win.gd.ptr, win.am.ptr,
@@ -823,6 +911,10 @@ class BatchedEKF:
         (optional); rows a filter does not reach are not written."""
         if self.layout != "aos" or self.flags & RUN_MIXED_PRECISION:
             raise ValueError("the fused front-end + filter kernel runs the FP64 filter on AoS state")
+        if self.noise is not None:   # (never silently with a scalar)
+            raise ValueError("the one-launch live kernels take one q and one r: feed a per-filter-noise filter "
+                             "through LiveSession (phase-3 events) or PhoneSession (a session from its first "
+                             "message, wire frames included) instead")
         traj_rows = int(traj_rows)
         if traj_rows < 0:
             raise ValueError("traj_rows must be >= 0")
@@ -853,6 +945,7 @@ class BatchedEKF:
         trajectory (R, batch, 4), record_dt_ns (R, batch) and record_times_ns (R, batch): a pose per record,
         from the same launch."""
         assert np.asarray(ev["types"]).shape[1] == self.batch
+        _scalar_noise_only(self, "run_events", "LiveSession")
         evb, E, flags = _event_planes(ev, events)
         init = DeviceBuffer(48 * self.batch).upload(
             np.concatenate([ev["init_acc"], ev["init_mag"]], axis=1).astype(np.float64))
@@ -961,12 +1054,13 @@ class _ChunkedSession:
         return out
 
     def snapshot(self):
-        """The session as host data: dict(batch, q, r, the class's scalars, its device buffers -- the session
+        """The session as host data: dict(batch, q, r (arrays for a per-filter-noise filter), the class's scalars, its device buffers -- the session
         state(s) as bytes (uint8 arrays) -- X, P and the host-side bookkeeping).  restore continues from it on
         another BatchedEKF or device."""
         K = self.batch
         X, P = self.filters.get_state()
-        snap = dict(batch=K, q=self.filters.q, r=self.filters.r, X=X, P=P, book=copy.deepcopy(self._book))
+        snap = dict(batch=K, q=copy.copy(self.filters.q), r=copy.copy(self.filters.r), X=X, P=P,
+                    book=copy.deepcopy(self._book))
         snap.update((name, getattr(self, name)) for name in self._FIELDS)
         for name, cols in self._BUFFERS.items():
             buf = getattr(self, "_" + name)
@@ -975,10 +1069,10 @@ class _ChunkedSession:
 
     @classmethod
     def restore(cls, filters, snapshot):
-        """A session that continues `snapshot` on `filters` (same batch, q and r; set the device first to move a
-        shard): its X / P are set to the snapshot's, the buffers are uploaded as they were."""
+        """A session that continues `snapshot` on `filters` (same batch, q and r -- for per-filter noise the same
+        arrays, compared with np.array_equal; set the device first to move a shard): its X / P are set to the snapshot's, the buffers are uploaded as they were."""
         s = snapshot
-        if filters.batch != s["batch"] or (filters.q, filters.r) != (s["q"], s["r"]):
+        if filters.batch != s["batch"] or not filters.same_noise(s["q"], s["r"]):
             raise ValueError("restore needs a BatchedEKF of the snapshot's batch, q and r")
         self = cls._from_snapshot(filters, s)
         filters.set_state(s["X"], s["P"])
@@ -1068,10 +1162,13 @@ class LiveSession(_ChunkedSession):
         n_events, flags = int(n_events), int(flags) | self._form
         self._rows_in(planes, n_events, offset, K * (32 if self._form else 16))
         tj = _Trajectory(chunk_trajectory_rows(trajectory, n_events) if trajectory is True else trajectory, n_events, K)
-        check(lib.pekf_live_resume_dev(K, n_events, planes.ptr + offset, self._init.ptr, self._t_init.ptr, self.alpha,
-                                       f.X.ptr, f.P.ptr, f.q, f.r, self._cnt.ptr, self._refs.ptr, flags,
-                                       self._state.ptr, int(self._book["started"]), tj.traj.ptr if tj.rows else None,
-                                       tj.dt.ptr if tj.rows else None, tj.rows, None, None))
+        # (a per-filter-noise filter: the same launch with its {q, r} plane in place of q and r)
+        entry, noise = ((lib.pekf_live_resume_dev, (f.q, f.r)) if f.noise is None else
+                        (lib.pekf_live_resume_noise_dev, (f.noise.ptr,)))
+        check(entry(K, n_events, planes.ptr + offset, self._init.ptr, self._t_init.ptr, self.alpha,
+                    f.X.ptr, f.P.ptr, *noise, self._cnt.ptr, self._refs.ptr, flags,
+                    self._state.ptr, int(self._book["started"]), tj.traj.ptr if tj.rows else None,
+                    tj.dt.ptr if tj.rows else None, tj.rows, None, None))
         out = self._after_launch(tj)
         return out if tj.wanted else out[0]
 
@@ -1331,10 +1428,12 @@ class PhoneSession(_ChunkedSession):
                                                 int(self._book["started"]), None))
         tj = _Trajectory(chunk_trajectory_rows(trajectory, E3) if trajectory is True else trajectory, E3, K)
         # (no rows: any valid pointer, none is read)
-        check(lib.pekf_live_join_dev(K, E3, ev3 if E3 else self._state.ptr, self._init.ptr, self._t_init.ptr,
-                                     self.alpha, f.X.ptr, f.P.ptr, f.q, f.r, self._cnt.ptr, self._refs.ptr,
-                                     EV_F64_EVENTS, self._state.ptr, tj.traj.ptr if tj.rows else None,
-                                     tj.dt.ptr if tj.rows else None, tj.rows, None, None))
+        entry, noise = ((lib.pekf_live_join_dev, (f.q, f.r)) if f.noise is None else
+                        (lib.pekf_live_join_noise_dev, (f.noise.ptr,)))   # (per-filter noise: its {q, r} plane)
+        check(entry(K, E3, ev3 if E3 else self._state.ptr, self._init.ptr, self._t_init.ptr,
+                    self.alpha, f.X.ptr, f.P.ptr, *noise, self._cnt.ptr, self._refs.ptr,
+                    EV_F64_EVENTS, self._state.ptr, tj.traj.ptr if tj.rows else None,
+                    tj.dt.ptr if tj.rows else None, tj.rows, None, None))
         out = self._after_launch(tj)
         return out[:1] + (self._ready.download((K,), np.int32).astype(bool),) + out[1:]
 
@@ -1343,7 +1442,7 @@ class PhoneSession(_ChunkedSession):
         if first.any():
             self._book["t_init"] = np.where(first, self._t_init.download((self.batch,), np.int64), self._book["t_init"])
 
-    def recycle(self, columns, t_start=None, X0=None, P0=None, final=False):
+    def recycle(self, columns, t_start=None, X0=None, P0=None, final=False, q=None, r=None):
         """The phones of `columns` leave and the next ones start afresh (pekf_session_recycle_dev, one launch): each
         listed column returns to the state a brand-new session gives it -- calibration (a session with n_cal),
         phase 2 and the filter -- and every other column goes on as if nothing had happened.  Fed a new phone's
@@ -1357,6 +1456,10 @@ class PhoneSession(_ChunkedSession):
         P = I, BatchedEKF.reset's).  final=True returns dict(X (n, 4), P (n, 4, 4), total_counts (n,)) of the
         departing phones, in the order of `columns` -- their last poses from the same launch, not a download of
         every column; otherwise None.  The columns' total_counts and record times start again.
+        q, r (a per-filter-noise filter only; both or neither): the new phones' noise, scalars or (n,) values,
+        validated as BatchedEKF's and written into those entries of filters.noise (BatchedEKF.set_noise) before
+        the recycle launch -- the one point at which a live column's noise may change, since its filter starts
+        afresh.  None: the columns keep the noise they had.
 
         LiveSession has no recycle: its lanes start from one launch-wide `resume` word, and a per-lane fresh start
         there needs the joining kernels on f32 events, which do not exist."""
@@ -1365,6 +1468,13 @@ class PhoneSession(_ChunkedSession):
         n = len(cols)
         if (X0 is None) != (P0 is None):
             raise ValueError("X0 needs P0 (and P0 needs X0)")
+        if (q is None) != (r is None):
+            raise ValueError("q needs r (and r needs q)")
+        if q is not None:
+            if self.filters.noise is None:
+                raise ValueError("recycle(q=, r=) needs a per-filter-noise filter: construct BatchedEKF with array "
+                                 "q / r (a scalar-noise filter has one q and one r for every column)")
+            q, r = _noise_arrays(q, r, n, "listed column")
         for name, a, shape in (("t_start", t_start, (n,)), ("X0", X0, (n, 4)), ("P0", P0, (n, 4, 4))):
             if a is not None and np.shape(a) != shape:
                 raise ValueError("%s must have shape %s for %d columns" % (name, shape, n))
@@ -1380,6 +1490,8 @@ class PhoneSession(_ChunkedSession):
                 None if t_start is None else DeviceBuffer(8 * n).upload(t0)]
         ptr = [b.ptr if b is not None else None for b in bufs]
         f = self.filters
+        if q is not None:
+            f.set_noise(cols, q, r)
         p1 = None
         if self._phase1 is not None:
             p1 = (self._p1state.ptr, self.n_cal, self._cal.ptr, self._fit.ptr, self._status.ptr)

@@ -322,6 +322,8 @@ class MultiDeviceEKF:
     def __init__(self, devices, batch_per_device, window, q=1.0, r=0.1, precision="f64"):
         from . import engine
 
+        if np.ndim(q) or np.ndim(r):   # (scalar-only: one q and one r for every device's filters)
+            raise ValueError("MultiDeviceEKF takes scalar q and r; per-filter noise is engine.BatchedEKF's")
         self.devices = [int(d) for d in devices]
         self.batch = int(batch_per_device)
         self.window = int(window)

@@ -10,6 +10,9 @@
                 and 342 chunks beside the one launch, f32 and FP64 events (profiles/r15/live_resume/)
   phone_session PEKF_AUX_ONLY=phone_session, that case alone: pekf_frontend_init_resume_dev + pekf_live_join_dev per
                 chunk beside one-shot phase 2 + pekf_live_resume_dev, 1, 8 and 64 chunks (profiles/r16/live_start/)
+  noise_per_filter PEKF_AUX_ONLY=noise_per_filter, that case alone: the per-filter-noise kernels beside the scalar ones,
+                same-box A B B A: the multi-record launch at config 3's shape, and a LiveSession's launches over
+                1,048,576 x 1,024 f32 events as one chunk and as 64 (profiles/r21/noise_per_filter/)
   gyro_chain    pekf_gyro_chain_dev (§8f-3): 16 B read per filter-record
   wahba_stream  pekf_wahba_stream_dev (§8f-3): 24 B read + 32 B written per filter-record
   predict_dev / correct_dev   per-call operators at n = 1M items (device pointers)
@@ -326,10 +329,101 @@ def phone_session(s, K0=16384, E=1024, tile=64, n_avg=100):
     return res
 
 
+def noise_per_filter(s, K0=16384, E=1024, tile=64):
+    """Per-filter noise beside launch-wide noise, a same-box A B B A (a: the scalar kernel, b: the per-filter one)
+    of (1) the multi-record launch at config 3's shape, 1,048,576 filters x 10,000 records over the 1,024-row
+    window (pekf_run_dev against pekf_run_noise_dev) and (2) a live session of 1,048,576 filters x 1,024 f32
+    events, FP64 records, as one chunk and as 64 chunks of 16 (pekf_live_resume_dev against
+    pekf_live_resume_noise_dev).  The plane holds the four pairs the tests run at, dealt as b % 4; the scalar
+    launches run at the first pair.  Leg c runs the per-filter kernels on a uniform plane (every lane the first
+    pair), which tells the kernels' form from the data; the config-3 part also times the scalar launch with the
+    compiler's own schedule (d) and at each of the four pairs.  24 B more are read per filter and launch."""
+    pairs = np.array([(1.0, 0.1), (0.37, 2.5), (4.0, 0.01), (1e-3, 1.0)])
+    B, W, N = 1 << 20, 1024, 10000
+    res = {"pairs": pairs.tolist()}
+    fa = engine.BatchedEKF(B)
+    fb = engine.BatchedEKF(B, q=pairs[np.arange(B) % 4, 0], r=pairs[np.arange(B) % 4, 1])
+    win = engine.IMUWindow(B, W).synthesize(stream=s)
+    # two more legs tell the kernel's form from its schedule and from its data: c, the per-filter kernel on a
+    # uniform plane (every lane the scalar launch's pair), and d, the scalar launch with the compiler's own
+    # schedule (PEKF_RUN_PIN=0), which is the schedule the per-filter kernels over 40 B records have
+    fc = engine.BatchedEKF(B, q=np.full(B, 1.0), r=np.full(B, 0.1))
+    abba = []
+    for name, f in (("a", fa), ("b", fb), ("c", fc), ("d", fa), ("d", fa), ("c", fc), ("b", fb), ("a", fa)):
+        f.reset(s)
+        if name == "d":
+            os.environ["PEKF_RUN_PIN"] = "0"
+        abba.append((name, timed(lambda: f.run_async(win, N, 0, s), s)))
+        os.environ.pop("PEKF_RUN_PIN", None)
+    a_ms, b_ms, c_ms, d_ms = (float(np.mean([m for n, m in abba if n == which])) for which in "abcd")
+    res["run_config3"] = {"filters": B, "records": N, "window": W, "abba_ms": abba, "a_scalar_ms": a_ms,
+                          "b_per_filter_ms": b_ms, "c_per_filter_uniform_plane_ms": c_ms, "d_scalar_no_pin_ms": d_ms,
+                          "b_over_a": b_ms / a_ms, "c_over_a": c_ms / a_ms, "d_over_a": d_ms / a_ms,
+                          "x_finite": bool(np.isfinite(fb.X.download((B, 4), np.float64)).all())}
+    log("config 3 launch: scalar %.2f ms, per-filter %.2f ms, per-filter on a uniform plane %.2f ms, scalar without "
+        "PIN %.2f ms (%s)" % (a_ms, b_ms, c_ms, d_ms, abba))
+    # ... and the scalar launch at each of the other pairs: what the data alone costs
+    per_pair = []
+    for qp, rp in pairs:
+        fp = engine.BatchedEKF(B, q=float(qp), r=float(rp))
+        per_pair.append(timed(lambda: fp.run_async(win, N, 0, s), s))
+        del fp
+    res["run_config3"]["scalar_ms_at_each_pair"] = per_pair
+    log("config 3 launch, scalar, at each pair: %s" % per_pair)
+    del win
+
+    ev = bench_events(K0, E)
+    K, row = K0 * tile, 16
+    assert K == B
+    init = np.tile(np.concatenate([ev["init_acc"], ev["init_mag"]], axis=1), (tile, 1))
+    ib = engine.DeviceBuffer(init.nbytes).upload(init)
+    tb = engine.DeviceBuffer(8 * K).upload(np.tile(ev["t_init"], tile).astype(np.int64))
+    cnt, refs = engine.DeviceBuffer(4 * K), engine.DeviceBuffer(48 * K)
+    src = synth.pack_events(ev)
+    assert src.shape[0] == E and not synth.has_time_events(src)
+    evb = engine.DeviceBuffer(E * K * row)
+    for e0 in range(0, E, 64):   # tiled and uploaded 64 rows at a time
+        blk = np.ascontiguousarray(np.tile(src[e0:e0 + 64], (1, tile, 1)))
+        check(lib.pekf_memcpy_h2d(evb.ptr + e0 * K * row, blk.ctypes.data, blk.nbytes, None))
+    del src, blk
+    state = engine.DeviceBuffer(int(lib.pekf_live_state_bytes(K, 0)))
+
+    def session(f, sizes):
+        entry, noise = ((lib.pekf_live_resume_dev, (f.q, f.r)) if f.noise is None else
+                        (lib.pekf_live_resume_noise_dev, (f.noise.ptr,)))
+
+        def run():
+            e0 = 0
+            for i, n in enumerate(sizes):
+                check(entry(K, n, evb.ptr + e0 * K * row, ib.ptr, tb.ptr, 0.1, f.X.ptr, f.P.ptr, *noise, cnt.ptr,
+                            refs.ptr, 0, state.ptr, int(i > 0), None, None, 0, None, s))
+                e0 += n
+        return run
+    for name, sizes in (("live_1x1024", [E]), ("live_64x16", [16] * 64)):
+        abba = []
+        for which, f in (("a", fa), ("b", fb), ("c", fc), ("c", fc), ("b", fb), ("a", fa)):   # (c: a uniform plane)
+            f.reset(s)
+            abba.append((which, timed(session(f, sizes), s)))
+        a_ms, b_ms, c_ms = (float(np.mean([m for n, m in abba if n == which])) for which in "abc")
+        res[name] = {"filters": K, "events_per_filter": E, "launches": len(sizes), "abba_ms": abba,
+                     "a_scalar_ms": a_ms, "b_per_filter_ms": b_ms, "c_per_filter_uniform_plane_ms": c_ms,
+                     "b_over_a": b_ms / a_ms, "c_over_a": c_ms / a_ms,
+                     "extra_us_per_launch": (b_ms - a_ms) / len(sizes) * 1e3,
+                     "uniform_extra_us_per_launch": (c_ms - a_ms) / len(sizes) * 1e3,
+                     "x_finite": bool(np.isfinite(fb.X.download((K, 4), np.float64)).all())}
+        log("%s: scalar %.3f ms, per-filter %.3f ms, per-filter on a uniform plane %.3f ms (%s)" %
+            (name, a_ms, b_ms, c_ms, abba))
+    res["device"] = engine.device_name(0)
+    return res
+
+
 def main():
     st = engine.Stream()
     s = st.handle
     res = {}
+    if os.environ.get("PEKF_AUX_ONLY") == "noise_per_filter":
+        print(json.dumps({"noise_per_filter": noise_per_filter(s)}))
+        return
     if os.environ.get("PEKF_AUX_ONLY") == "live_resume":
         print(json.dumps({"live_resume": live_resume(s)}))
         return
