@@ -568,6 +568,52 @@ int pekf_session_recycle_dev(int64_t batch, int64_t n_cols, const int32_t *cols,
                              int64_t *t_init, int32_t *ready, const int64_t *t_start_new, void *magcal_state,
                              int n_cal, double *cal, double *fit, int32_t *status, void *stream);
 
+/* A live phone moves: pekf_session_recycle_dev's counterpart.  Where that call writes a listed column's fresh
+ * form, these two copy its live form: pekf_session_export_dev gathers the listed columns of a chunked session
+ * into one packed buffer, pekf_session_import_dev scatters a packed buffer into the listed columns of a session
+ * -- the same one or another, of another batch.  The reference has no counterpart (one client per process,
+ * KFS/Server.cpp:58, :93: a phone never changes its place); a batch uses it to gather the survivors of a sparse
+ * session into a smaller one, to hand a few phones to another shard, or to fork a phone.  An imported column,
+ * fed the phone's next rows, gives bit for bit what the column it came from would have given.
+ *   pack: a device buffer of pekf_session_columns_bytes(n_cols, n_cal, flags) bytes, 16-byte aligned.  Its layout
+ * is private, as the session states' are: lane-minor planes over the n_cols listed columns, entry i the column
+ * cols[i].  Its bytes may be copied as they are, to the host and back or to another device.  Going through it is
+ * what makes source and destination independent: nothing is copied in place.
+ *   cols, batch and the three optional groups are pekf_session_recycle_dev's (a group whose state pointer is NULL
+ * is not touched, a group given in part is PEKF_ERR_INVALID), without that call's per-column inputs:
+ *   the filter (live_state, X, P, refs; flags must be PEKF_EV_F64_EVENTS): the column's 16 bytes of every plane
+ * of the state -- the join mark among them --, X[col], P[col] (AoS) and refs[col];
+ *   phase 2 (init_state, t_start, init, t_init, ready; flags must be PEKF_EV_F64_EVENTS too -- the pack of a
+ * joining session has room for both groups, a pack of flags 0 for neither): the state's planes and the four
+ * per-column values;
+ *   phase 1 (magcal_state, n_cal, cal, fit, status; n_cal in [6, 2^30), the session's AND the pack's; either
+ * flags): the two header planes, all n_cal stored samples and the outputs.  Without this group n_cal must be 0.
+ *   The checks, their wording and their order are pekf_session_recycle_dev's: no negative size, batch < 2^28, the
+ * three states and the pack 16-byte aligned, groups whole, n_cal, flags, n_cols <= batch.  n_cols == 0 or
+ * batch == 0: PEKF_OK, no launch.
+ *   THE CALLER'S PRECONDITIONS, not checked: cols lists DISTINCT columns inside [0, batch) (one lane per listed
+ * column; an index outside reads and writes nothing, two equal ones would write one column twice on import); a
+ * pack carries the groups it was exported with, in a layout fixed by (n_cols, n_cal, flags), so an import takes
+ * the same n_cols, n_cal and flags and no group the export did not have (those planes were never written).  The
+ * noise is not in the pack: the filter's state holds its covariance scaled by the column's r
+ * (pekf_live_join_noise_dev), so the destination column must run with the q and r the source column had. */
+int pekf_session_export_dev(int64_t batch, int64_t n_cols, const int32_t *cols, uint32_t flags,
+                            const void *live_state, const double *X, const double *P, const double *refs,
+                            const void *init_state, const int64_t *t_start, const double *init,
+                            const int64_t *t_init, const int32_t *ready, const void *magcal_state, int n_cal,
+                            const double *cal, const double *fit, const int32_t *status, void *pack, void *stream);
+int pekf_session_import_dev(int64_t batch, int64_t n_cols, const int32_t *cols, uint32_t flags, void *live_state,
+                            double *X, double *P, double *refs, void *init_state, int64_t *t_start, double *init,
+                            int64_t *t_init, int32_t *ready, void *magcal_state, int n_cal, double *cal, double *fit,
+                            int32_t *status, const void *pack, void *stream);
+/* The bytes of a pack of n_cols columns (host only), a multiple of 16: with flags == PEKF_EV_F64_EVENTS the
+ * filter and phase-2 groups of a joining session, with flags == 0 neither; with n_cal != 0 the phase-1 group
+ * too (n_cal == 0: none), per column the phase-1 state's own size, ((24 n_cal + 15) & ~15) + 32, and the outputs.
+ * < 0: a negative n_cols or one of 2^28 or more, n_cal neither 0 nor in [6, 2^30), any other flags.  64 bits,
+ * spelled as pekf_live_state_bytes is. */
+long long
+int pekf_session_columns_bytes(int64_t n_cols, int n_cal, uint32_t flags);
+
 /* The wire on the device: the clients' 100-byte frames (as MessageSender.java:217-233 sends and Server.cpp:35,84
  * receives them: "#<phase>,<type>:<x>,<y>,<z>,t:<ns>", spaces to 99 characters, '\n') -> FP64 event planes.
  * frames: [n_frames][batch][100] bytes (device; 4-byte aligned), phone b's frames in order along the first

@@ -147,6 +147,9 @@ SIGNATURES = {
     "pekf_frontend_init_resume_dev": [_i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _u32, _vp, _int, _vp],
     "pekf_frontend_init_state_bytes": [_i64, _u32],
     "pekf_session_recycle_dev": [_i64, _i64, _vp, _u32] + [_vp] * 8 + [_vp] * 6 + [_vp, _int, _vp, _vp, _vp] + [_vp],
+    "pekf_session_export_dev": [_i64, _i64, _vp, _u32] + [_vp] * 4 + [_vp] * 5 + [_vp, _int, _vp, _vp, _vp] + [_vp, _vp],
+    "pekf_session_import_dev": [_i64, _i64, _vp, _u32] + [_vp] * 4 + [_vp] * 5 + [_vp, _int, _vp, _vp, _vp] + [_vp, _vp],
+    "pekf_session_columns_bytes": [_i64, _int, _u32],
     "pekf_log_scan": [ctypes.c_char_p, ctypes.POINTER(_i64)],
     "pekf_log_read": [ctypes.c_char_p, _i64, _vp, _vp, _vp, _vp, _dp, _dp, _dp],
     "pekf_log_read_ext": [ctypes.c_char_p, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64), _dp, _dp, _dp],
@@ -169,7 +172,8 @@ SIGNATURES = {
     "pekf_allreduce_max_dev": [_vp, _vp, _i64, _vp],
 }
 _RESTYPE = {"pekf_abi_version": ctypes.c_int, "pekf_last_error": ctypes.c_char_p, "pekf_live_state_bytes": _i64,
-            "pekf_frontend_init_state_bytes": _i64, "pekf_magcal_state_bytes": _i64}
+            "pekf_frontend_init_state_bytes": _i64, "pekf_magcal_state_bytes": _i64,
+            "pekf_session_columns_bytes": _i64}
 
 
 def _load():

@@ -987,6 +987,89 @@ def _launch_recycle(batch, cols, filter_group=None, phase2_group=None, phase1_gr
     check(lib.pekf_device_sync())
 
 
+def _launch_move(entry, batch, cols, flags, pack, filter_group=None, phase2_group=None, phase1_group=None):
+    """pekf_session_export_dev / pekf_session_import_dev (entry) on the host list cols and the DeviceBuffer pack,
+    run to completion.  The groups are the entries', as tuples in their argument order: (state, X, P, refs),
+    (state, t_start, init, t_init, ready), (state, n_cal, cal, fit, status)."""
+    dev = DeviceBuffer(4 * len(cols)).upload(cols)
+    f, p2, p1 = filter_group or (None,) * 4, phase2_group or (None,) * 5, phase1_group or (None, 0, None, None, None)
+    check(entry(batch, len(cols), dev.ptr, flags, *f, *p2, *p1, pack.ptr, None))
+    check(lib.pekf_device_sync())
+
+
+class SessionColumns:
+    """Live phones out of their session (PhoneSession.export_columns, CalibrationSession.export_columns): the
+    columns' device state in one packed DeviceBuffer (pekf_session_export_dev; its layout is private) and what
+    the host holds for them.  import_columns of a session with the same n_avg, alpha and n_cal takes them, in
+    this object's order; to_host / from_host carry them to another process or device.
+
+    kind: "phone" (a PhoneSession's columns: the filter, phase 2 and, with n_cal, phase 1) or "calibration" (a
+    CalibrationSession's: phase 1 alone); n: the columns; n_avg, alpha (a phone's), n_cal (None: no phase 1),
+    events; q, r (n,): the columns' noise -- the session state holds the covariance scaled by r, so they travel
+    with it; book: the columns' rows of the session's host book, dict of (n,) arrays (a phone's t_init, dt_sum,
+    total_counts; an f32 calibration's last_times)."""
+
+    def __init__(self, kind, pack, n, n_avg, alpha, n_cal, events, q, r, book):
+        self.kind, self.pack, self.n = kind, pack, int(n)
+        self.n_avg, self.alpha, self.n_cal, self.events = n_avg, alpha, n_cal, events
+        self.q, self.r, self.book = q, r, book
+
+    @property
+    def flags(self):
+        """the pack's flags (pekf_session_columns_bytes): a phone's pack is a joining session's"""
+        return EV_F64_EVENTS if self.kind == "phone" else 0
+
+    @staticmethod
+    def nbytes(n, n_cal, flags):
+        nbytes = int(lib.pekf_session_columns_bytes(n, n_cal or 0, flags))
+        if nbytes < 0:
+            raise ValueError("no pack for %d columns with n_cal=%r" % (n, n_cal))
+        return nbytes
+
+    def to_host(self):
+        """The object as a dict of NumPy arrays (the pack's bytes as uint8; scalars as 0-d arrays, -1 for a
+        missing n_avg / n_cal and NaN for a missing alpha); from_host rebuilds it."""
+        d = dict(kind=np.array(self.kind), events=np.array(self.events), n=np.array(self.n, np.int64),
+                 n_avg=np.array(-1 if self.n_avg is None else self.n_avg, np.int64),
+                 n_cal=np.array(-1 if self.n_cal is None else self.n_cal, np.int64),
+                 alpha=np.array(np.nan if self.alpha is None else self.alpha, np.float64),
+                 q=self.q.copy(), r=self.r.copy(), pack=self.pack.download((self.pack.nbytes,), np.uint8))
+        d.update(("book_" + name, rows.copy()) for name, rows in self.book.items())
+        return d
+
+    @classmethod
+    def from_host(cls, d):
+        """to_host's dict as an object on the current device (set_device first to move a phone to another one)"""
+        kind, n = str(d["kind"]), int(d["n"])
+        if kind not in ("phone", "calibration"):
+            raise ValueError("kind must be 'phone' or 'calibration'")
+        n_avg, n_cal = (None if int(d[key]) < 0 else int(d[key]) for key in ("n_avg", "n_cal"))
+        alpha = None if np.isnan(d["alpha"]) else float(d["alpha"])
+        book = {key[5:]: np.array(rows) for key, rows in d.items() if key.startswith("book_")}
+        q, r = np.array(d["q"], np.float64), np.array(d["r"], np.float64)
+        pack = np.ascontiguousarray(d["pack"], np.uint8)
+        if any(np.shape(a) != (n,) for a in (q, r) + tuple(book.values())):
+            raise ValueError("q, r and the book rows must have one entry per column")
+        if pack.shape != (cls.nbytes(n, n_cal, EV_F64_EVENTS if kind == "phone" else 0),):
+            raise ValueError("the pack's bytes are not those of %d columns with n_cal=%r" % (n, n_cal))
+        buf = DeviceBuffer(pack.nbytes)
+        if pack.nbytes:
+            buf.upload(pack)
+        return cls(kind, buf, n, n_avg, alpha, n_cal, str(d["events"]), q, r, book)
+
+
+def _import_refusals(session, kind, cols, pack, fields):
+    """import_columns' refusals that do not depend on the session's class, before any launch"""
+    if not isinstance(pack, SessionColumns) or pack.kind != kind:
+        raise ValueError("import_columns takes the SessionColumns of a session of this class (export_columns)")
+    if len(cols) != pack.n:
+        raise ValueError("%d columns listed for a pack of %d" % (len(cols), pack.n))
+    for name in fields:
+        if getattr(session, name) != getattr(pack, name):
+            raise ValueError("the pack's %s is %r, the session's %r: a phone moves between sessions of the same "
+                             "n_avg, alpha and n_cal" % (name, getattr(pack, name), getattr(session, name)))
+
+
 class _ChunkedSession:
     """A session fed in chunks, what LiveSession and PhoneSession share: the filters it refuses, the host
     bookkeeping (the summed counts, the running record times), what follows a chunk's launch, and snapshot /
@@ -1245,6 +1328,40 @@ class CalibrationSession:
             self.launch(None, 0)
         _launch_recycle(self.batch, cols, phase1_group=(self._state.ptr, self.n_cal, self._cal.ptr, self._fit.ptr,
                                                         self._status.ptr))
+
+    def _group(self):
+        return self._state.ptr, self.n_cal, self._cal.ptr, self._fit.ptr, self._status.ptr
+
+    def export_columns(self, columns, release=True):
+        """The phones of `columns` (recycle's rule) as a SessionColumns object: their sums, counts, stored samples
+        and outputs in one device pack (pekf_session_export_dev, the phase-1 group alone) and, on f32 events,
+        their rows of the last-times book.  release=True: the columns are then recycled -- the phones have left
+        this session; release=False: they go on as they were (a fork).  Either event form."""
+        cols = _recycle_columns(columns, self.batch)
+        n = len(cols)
+        pack = DeviceBuffer(SessionColumns.nbytes(n, self.n_cal, 0))
+        if n and not self.started:
+            self.launch(None, 0)
+        if n:
+            _launch_move(lib.pekf_session_export_dev, self.batch, cols, 0, pack, phase1_group=self._group())
+        out = SessionColumns("calibration", pack, n, None, None, self.n_cal, self.events, np.zeros(n), np.zeros(n),
+                             dict(last_times=self._last_times[cols].copy()))
+        if release and n:
+            self.recycle(cols)
+        return out
+
+    def import_columns(self, columns, pack):
+        """The pack's phones (a CalibrationSession's export_columns, of the same n_cal and event form) into the
+        listed columns, in the pack's order, overwriting what those columns held (pekf_session_import_dev).
+        Refused, before any launch: another number of columns than the pack's, another n_cal or event form."""
+        cols = _recycle_columns(columns, self.batch)
+        _import_refusals(self, "calibration", cols, pack, ("n_cal", "events"))
+        if len(cols) == 0:
+            return
+        if not self.started:
+            self.launch(None, 0)
+        _launch_move(lib.pekf_session_import_dev, self.batch, cols, 0, pack.pack, phase1_group=self._group())
+        self._last_times[cols] = pack.book["last_times"]
 
     def result(self):
         """calibrate_magnetometer's dict (bias, W, fit, status, calibrated, cal, status_dev) from what has been
@@ -1507,6 +1624,82 @@ class PhoneSession(_ChunkedSession):
         book["dt_sum"][cols] = 0.0
         book["t_init"][cols] = t0
         return out
+
+    _BOOK_ROWS = ("t_init", "dt_sum", "total_counts")
+
+    def _move_groups(self):
+        """the session's three groups as _launch_move takes them (phase 1: a session with n_cal only)"""
+        f, p1 = self.filters, None
+        if self._phase1 is not None:
+            p1 = (self._p1state.ptr, self.n_cal, self._cal.ptr, self._fit.ptr, self._status.ptr)
+        return ((self._state.ptr, f.X.ptr, f.P.ptr, self._refs.ptr),
+                (self._p2state.ptr, self._t_start.ptr, self._init.ptr, self._t_init.ptr, self._ready.ptr), p1)
+
+    def export_columns(self, columns, release=True):
+        """The live phones of `columns` (recycle's rule: distinct indices in [0, K), any order) as a SessionColumns
+        object, in that order: everything the session holds for them on the device -- the calibration state and
+        outputs (a session with n_cal), phase 2's, the filter's with X, P and refs -- gathered into one pack by
+        one launch (pekf_session_export_dev), their q and r, and their rows of the host book.  Valid at any chunk
+        boundary, before the first chunk included (the session's zero-row launch runs first, as recycle's).
+        release=True: the listed columns are then recycled (recycle's own launch and book reset): the phones have
+        left this session, and import_columns brings them into free columns of this or another session, of any
+        batch -- a compaction, or through to_host / from_host a move to another device.  release=False: the
+        columns go on as they were, and the object is a fork of them.  An empty list launches nothing."""
+        K, f = self.batch, self.filters
+        cols = _recycle_columns(columns, K)
+        n = len(cols)
+        pack = DeviceBuffer(SessionColumns.nbytes(n, self.n_cal, EV_F64_EVENTS))
+        if n:
+            if not self._book["started"]:
+                self._feed_no_rows()
+            _launch_move(lib.pekf_session_export_dev, K, cols, EV_F64_EVENTS, pack, *self._move_groups())
+        q, r = (np.full(n, f.q), np.full(n, f.r)) if f.noise is None else (f.q[cols].copy(), f.r[cols].copy())
+        out = SessionColumns("phone", pack, n, self.n_avg, self.alpha, self.n_cal, "f64", q, r,
+                             {name: self._book[name][cols].copy() for name in self._BOOK_ROWS})
+        if release and n:
+            self.recycle(cols)
+        return out
+
+    def import_columns(self, columns, pack):
+        """The pack's phones (export_columns' SessionColumns, of this or another PhoneSession) into the listed
+        columns, in the pack's order, overwriting whatever those columns held (pekf_session_import_dev, one
+        launch); their book rows become the pack's.  Fed its next rows in its new column, a phone goes on bit
+        for bit as in the column it left: X, P, refs, ready, the counts, every trajectory row and record time,
+        the calibration.  Every other column is untouched.
+        Refused with ValueError, before any launch: columns that break recycle's rule or are not pack.n; a pack
+        whose n_avg, alpha or n_cal is not the session's (phase 1 on one side only included); noise that does not
+        fit -- the session state holds the covariance scaled by the column's r (BatchedEKF's docstring), so a
+        phone keeps its q and r: a per-filter-noise filter takes the pack's pairs into its plane
+        (BatchedEKF.set_noise), a scalar filter accepts only pairs equal to its own q and r."""
+        K, f = self.batch, self.filters
+        cols = _recycle_columns(columns, K)
+        _import_refusals(self, "phone", cols, pack, ("n_avg", "alpha", "n_cal"))
+        if f.noise is None:
+            if not (np.all(pack.q == f.q) and np.all(pack.r == f.r)):
+                raise ValueError("the pack's phones run with their own q and r, which are not this scalar-noise "
+                                 "filter's (q=%r, r=%r): import into a per-filter-noise filter" % (f.q, f.r))
+        else:
+            _noise_arrays(pack.q, pack.r, pack.n, "listed column")
+        if len(cols) == 0:
+            return
+        if not self._book["started"]:
+            self._feed_no_rows()
+        if f.noise is not None:
+            f.set_noise(cols, pack.q, pack.r)
+        _launch_move(lib.pekf_session_import_dev, K, cols, EV_F64_EVENTS, pack.pack, *self._move_groups())
+        for name in self._BOOK_ROWS:
+            self._book[name][cols] = pack.book[name]
+
+    def move(self, src, dst):
+        """import_columns(dst, export_columns(src)) within this session: the phones of src go on in the columns
+        dst (as many; dst[i] takes src[i]) and the columns of src are recycled.  src and dst must be disjoint --
+        a compaction moves phones into free columns; a permutation in place is refused, before any launch."""
+        src, dst = _recycle_columns(src, self.batch), _recycle_columns(dst, self.batch)
+        if len(src) != len(dst):
+            raise ValueError("%d columns listed for a pack of %d" % (len(dst), len(src)))
+        if len(np.intersect1d(src, dst)):
+            raise ValueError("src and dst overlap: a phone moves into a free column (no permutation in place)")
+        self.import_columns(dst, self.export_columns(src))
 
 
 class FilterHandle:

@@ -13,6 +13,10 @@
   noise_per_filter PEKF_AUX_ONLY=noise_per_filter, that case alone: the per-filter-noise kernels beside the scalar ones,
                 same-box A B B A: the multi-record launch at config 3's shape, and a LiveSession's launches over
                 1,048,576 x 1,024 f32 events as one chunk and as 64 (profiles/r21/noise_per_filter/)
+  session_move  PEKF_AUX_ONLY=session_move, that case alone: pekf_session_export_dev / pekf_session_import_dev on 1,
+                1,024 and every column of a 1,048,576-phone PhoneSession beside snapshot + restore, and a chunk's
+                launches in a sparse session against the compact one that adopted its phones
+                (profiles/r22/session_move/)
   gyro_chain    pekf_gyro_chain_dev (§8f-3): 16 B read per filter-record
   wahba_stream  pekf_wahba_stream_dev (§8f-3): 24 B read + 32 B written per filter-record
   predict_dev / correct_dev   per-call operators at n = 1M items (device pointers)
@@ -417,10 +421,135 @@ def noise_per_filter(s, K0=16384, E=1024, tile=64):
     return res
 
 
+def session_move(s, K0=16384, rows=16, tile=64, n_avg=20):
+    """Moving live phones (pekf_session_export_dev / pekf_session_import_dev) beside the only route there was,
+    snapshot + restore through the host.  An engine.PhoneSession of K0 * tile phones (FP64 events), started by one
+    `rows`-row chunk of every plane, with n_cal = 100 and without phase 1:
+      export_<n> / import_<n>   one launch each on n listed columns -- 1, 1,024 scattered, every column -- the
+                  import back into the columns the pack came from (idempotent, so repeats time the same work);
+      snapshot_restore          wall time of session.snapshot() + PhoneSession.restore on new filters, once.
+    Then what a compaction buys: the session's launches for a `rows`-row chunk when only every 16th column holds a
+    live phone (the others recycled, their rows empty), against a session of K / 16 columns that adopted those
+    phones (export_columns + import_columns) fed the same phones' rows.  Nothing is asserted about the times."""
+    from poseestimationkf_amd._lib import EV_F64_EVENTS
+    K, row = K0 * tile, 32 * K0 * tile
+    ev = synth.generate_events(np.arange(K0), 3 * rows, seed=12)
+
+    def tiled(planes, t):   # host FP64 planes (E, k0, 4) -> a device buffer [E][k0 * t] double4, each row tiled
+        E, k0 = planes.shape[:2]
+        src, dst = engine.DeviceBuffer(planes.nbytes).upload(planes), engine.DeviceBuffer(planes.nbytes * t)
+        for e in range(E):
+            for i in range(t):
+                check(lib.pekf_memcpy_d2d(dst.ptr + 32 * k0 * (e * t + i), src.ptr + 32 * k0 * e, 32 * k0, s))
+        check(lib.pekf_stream_sync(s))
+        return dst
+
+    def chunk_of(sess, evb):
+        k, f, r = sess.batch, sess.filters, 32 * sess.batch * rows
+        ev1, ev2, ev3 = evb.ptr, evb.ptr + r, evb.ptr + 2 * r
+
+        def chunk():
+            if sess.n_cal is not None:
+                check(lib.pekf_magcal_resume_dev(k, rows, ev1, sess.n_cal, sess._cal.ptr, sess._fit.ptr, sess._status.ptr,
+                                                 EV_F64_EVENTS, sess._p1state.ptr, 1, s))
+                for p in (ev2, ev3):
+                    check(lib.pekf_magcal_apply_dev(k, rows, p, sess._cal.ptr, sess._status.ptr, EV_F64_EVENTS, s))
+            check(lib.pekf_frontend_init_resume_dev(k, rows, ev2, sess._t_start.ptr, sess.n_avg, sess._init.ptr,
+                                                    sess._t_init.ptr, sess._ready.ptr, EV_F64_EVENTS, sess._p2state.ptr,
+                                                    1, s))
+            check(lib.pekf_live_join_dev(k, rows, ev3, sess._init.ptr, sess._t_init.ptr, sess.alpha, f.X.ptr, f.P.ptr,
+                                         f.q, f.r, sess._cnt.ptr, sess._refs.ptr, EV_F64_EVENTS, sess._state.ptr, None,
+                                         None, 0, None, s))
+        return chunk
+
+    host = synth.pack_events64(ev, ev["values"].astype(np.float64))
+    evb = tiled(host, tile)
+    rng = np.random.default_rng(3)
+    lists = {"1": np.array([K // 3], np.int32), "1024": rng.choice(K, min(1024, K), replace=False).astype(np.int32),
+             "all": np.arange(K, dtype=np.int32)}
+    res = {"phones": K, "rows_per_plane": rows}
+    for n_cal in (100, None):
+        sess = engine.PhoneSession(engine.BatchedEKF(K), n_avg=n_avg, n_cal=n_cal)
+        sess.feed_planes(evb, rows, evb, rows, offset2=row * rows, offset3=row * 2 * rows,
+                         **(dict(planes1=evb, n1=rows) if n_cal else {}))
+        groups = sess._move_groups()
+        f, p2, p1 = groups[0], groups[1], groups[2] or (None, 0, None, None, None)
+        per_col = int(lib.pekf_session_columns_bytes(1, n_cal or 0, EV_F64_EVENTS))
+        out = {"n_cal": n_cal, "pack_bytes_per_column": per_col,
+               "state_bytes_per_phone": (sess._p2state.nbytes + sess._state.nbytes +
+                                         (sess._p1state.nbytes if n_cal else 0)) // K}
+        for name, cols in lists.items():
+            n = len(cols)
+            dev = engine.DeviceBuffer(cols.nbytes).upload(cols)
+            pack = engine.DeviceBuffer(per_col * n)
+
+            def move(entry, dev=dev, n=n, pack=pack):
+                return lambda: check(entry(K, n, dev.ptr, EV_F64_EVENTS, *f, *p2, *p1, pack.ptr, s))
+            e1, i1, i2, e2 = (timed(move(lib.pekf_session_export_dev), s, reps=9),
+                              timed(move(lib.pekf_session_import_dev), s, reps=9),
+                              timed(move(lib.pekf_session_import_dev), s, reps=9),
+                              timed(move(lib.pekf_session_export_dev), s, reps=9))
+            byts = 2 * n * per_col + 4 * n       # each launch reads and writes the columns' bytes once
+            out["move_" + name] = {"columns": n, "export_ms": [e1, e2], "import_ms": [i1, i2], "bytes_per_launch": byts,
+                                   "export_gbs": byts / (min(e1, e2) * 1e-3) / 1e9,
+                                   "import_gbs": byts / (min(i1, i2) * 1e-3) / 1e9,
+                                   "bytes_predict_ms": byts / (HBM * 1e9) * 1e3}
+            log("n_cal=%s, %s columns (%d): export %.4f / %.4f ms, import %.4f / %.4f ms; the bytes predict %.4f ms"
+                % (n_cal, name, n, e1, e2, i1, i2, out["move_" + name]["bytes_predict_ms"]))
+            del pack, dev
+        t0 = time.perf_counter()
+        snap = sess.snapshot()
+        t1 = time.perf_counter()
+        again = engine.PhoneSession.restore(engine.BatchedEKF(K), snap)
+        check(lib.pekf_device_sync())
+        t2 = time.perf_counter()
+        out["snapshot_restore"] = {"snapshot_ms": (t1 - t0) * 1e3, "restore_ms": (t2 - t1) * 1e3,
+                                   "host_bytes": int(sum(v.nbytes for v in snap.values() if isinstance(v, np.ndarray)))}
+        log("n_cal=%s: snapshot %.0f ms + restore %.0f ms through the host (%.2f GB)"
+            % (n_cal, (t1 - t0) * 1e3, (t2 - t1) * 1e3, out["snapshot_restore"]["host_bytes"] / 1e9))
+        del snap, again
+        res["n_cal_100" if n_cal else "no_phase1"] = out
+        if n_cal is None:
+            break
+        # ---- what a compaction buys (the calibrating session): every 16th column stays live
+        live = np.arange(0, K, 16, dtype=np.int32)
+        gone = np.setdiff1d(np.arange(K, dtype=np.int32), live)
+        full_ms = timed(chunk_of(sess, evb), s, reps=9)
+        sess.recycle(gone)
+        sparse_host = host.copy()
+        none = np.array([0, 0, 0, synth.EV64_NONE_W], np.uint64).view(np.float64)   # the FP64 no-message event
+        sparse_host[:, np.arange(K0) % 16 != 0] = none
+        evs = tiled(sparse_host, tile)
+        sparse_ms = [timed(chunk_of(sess, evs), s, reps=9)]
+        t0 = time.perf_counter()
+        small = engine.PhoneSession(engine.BatchedEKF(len(live)), n_avg=n_avg, n_cal=n_cal)
+        small.import_columns(np.arange(len(live)), sess.export_columns(live))
+        adopt_ms = (time.perf_counter() - t0) * 1e3
+        evl = tiled(np.ascontiguousarray(host[:, ::16]), tile)
+        small_ms = [timed(chunk_of(small, evl), s, reps=9)]
+        empty_ms = timed(chunk_of(sess, evs), s, reps=9)            # (now every column of it is free)
+        small_ms.append(timed(chunk_of(small, evl), s, reps=9))
+        sess.import_columns(live, small.export_columns(np.arange(len(live)), release=False))   # ... and live again
+        sparse_ms.append(timed(chunk_of(sess, evs), s, reps=9))
+        res["compaction"] = {"n_cal": n_cal, "columns": K, "live_phones": len(live), "full_session_chunk_ms": full_ms,
+                             "sparse_session_chunk_ms": sparse_ms, "compact_session_chunk_ms": small_ms,
+                             "emptied_session_chunk_ms": empty_ms, "adopt_wall_ms": adopt_ms,
+                             "live_total_counts": int(small.total_counts.sum())}
+        log("a %d-row chunk: %.3f ms with every column live, %s ms with %d of %d live, %s ms in a %d-column session "
+            "that adopted them (export + import, host side included: %.1f ms)"
+            % (rows, full_ms, sparse_ms, len(live), K, small_ms, len(live), adopt_ms))
+        del small, evs, evl, sess
+    res["device"] = engine.device_name(0)
+    return res
+
+
 def main():
     st = engine.Stream()
     s = st.handle
     res = {}
+    if os.environ.get("PEKF_AUX_ONLY") == "session_move":
+        print(json.dumps({"session_move": session_move(s, tile=int(os.environ.get("PEKF_AUX_TILE", "64")))}))
+        return
     if os.environ.get("PEKF_AUX_ONLY") == "noise_per_filter":
         print(json.dumps({"noise_per_filter": noise_per_filter(s)}))
         return
