@@ -193,7 +193,14 @@ PEKF_DEV void rotm_to_quat(const double *M, double *q) {
 // hardware v_rcp_f64 / v_rsq_f64 seed (measured on MI355X: <= 5.6e-8 relative) plus ONE Newton
 // step, measured <= 11 ulp (rcp) / <= 19 ulp (rsq), i.e. <= 4.2e-15 relative, over 1e-6..1e6
 // (scripts/probe_fp64.hip); a second step would give 0 / 2 ulp for 4 more FP64 ops each.
-// No scale / fixup sequences: operands here are positive and normal (DESIGN.md "FP64 budget").
+// No scale / fixup sequences.  The filter step's operands are positive and normal (DESIGN.md "FP64 budget");
+// phase 3's (pekf_phase3.hpp) are not all: recip takes a time difference that is negative when a clock steps back,
+// +-1 ns up to 2^45 ns, and 0 for two samples at one time (NaN out, as the reference's x / 0 ends in NaN); the
+// normalisation's rsqrt takes sums of squares from ~1e-146 (samples of 1e-80 times their gap in ns) to ~1e176,
+// 0 for an interpolant that is exactly zero (inf, then 0 * inf = NaN as the reference's 0 / 0) and +inf for an
+// infinite sample, where this Newton residual would be inf * 0: phase 3 normalises through rsqrt_sumsq, which
+// takes that case.  tests/test_frontend_conditioning.py holds both against exact chains over that whole range
+// (worst 24.5 u kappa on MI355X, the rsqrt's error class; bound 303 u kappa).
 constexpr int kNewtonSteps = 1;
 
 PEKF_DEV double recip(double x) {

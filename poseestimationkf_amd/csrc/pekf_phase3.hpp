@@ -69,17 +69,28 @@ __device__ __forceinline__ F3 sel(bool c, const F3 &a, const F3 &b) {
     return {c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z};
 }
 
+// rsqrt<true> (pekf_math.hpp: the hardware seed and one Newton step) of a sum of squares s, which a sample of
+// +-Infinity makes +inf: the seed is then 0 and the step's residual 1 - s y^2 would be inf * 0 = NaN, turning
+// the finite components of the record into NaN where the reference's v / sqrt(inf) gives 0 in them and NaN in
+// the infinite one alone.  The residual is formed from min(s, DBL_MAX) instead: 1 - DBL_MAX * 0 * 0 = 1 leaves
+// y = 0; for every finite s the minimum is s and the bits are rsqrt<true>'s; a NaN s still gives NaN (the seed).
+__device__ __forceinline__ double rsqrt_sumsq(double s) {
+    const double y = __builtin_amdgcn_rsq(s);
+    const double e = fma(-fmin(s, 0x1.fffffffffffffp+1023) * y, y, 1.0);  // 1 - s y^2
+    return fma(y, 0.5 * e, y);
+}
+
 // Parser::NormalizeValues (:221-228) with one rsqrt instead of a sqrt and three divisions
 __device__ __forceinline__ V3 normalised(const V3 &v) {
 #pragma clang fp contract(fast)
-    const double in = rsqrt<true>((v.x * v.x + v.y * v.y) + v.z * v.z);
+    const double in = rsqrt_sumsq((v.x * v.x + v.y * v.y) + v.z * v.z);
     return {v.x * in, v.y * in, v.z * in};
 }
 // The same with the sum of squares fused explicitly, fma(z, z, fma(y, y, x x)): which product of a sum of
 // products the compiler contracts depends on the code around it, and the FP64-event records of k_live and
 // k_frontend must round identically (normalised keeps the f32 form's rounding as it was)
 __device__ __forceinline__ V3 normalised_fma(const V3 &v) {
-    const double in = rsqrt<true>(__builtin_fma(v.z, v.z, __builtin_fma(v.y, v.y, v.x * v.x)));
+    const double in = rsqrt_sumsq(__builtin_fma(v.z, v.z, __builtin_fma(v.y, v.y, v.x * v.x)));
     return {v.x * in, v.y * in, v.z * in};
 }
 
