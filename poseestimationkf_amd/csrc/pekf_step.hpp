@@ -226,9 +226,18 @@ struct RowCursor {
 // constant after a launch's first record, and every launch shape (n records at once, one record
 // per launch, the handle's per-record update) rounds identically.  A state that is not unit (a
 // user's set_state) keeps its |X|^2, which the reference's Jb and RK4 use (:60-62).
+// The snap is an error of the one-record kernels' skip record, which stores z normalised by the snapped
+// |X|^2: half the window.  40 ulp of the rsqrt leave |X|^2 - 1 <= 2 * 4.2e-15 ~ 1e-14; kNormSnap is
+// three times that and costs at most 1.45e-14 = 131 u, inside the 303 Y u (Y >= 1) that
+// tests/test_step_halves.py holds the propagation to (at 1e-13 a set_state X of |X|^2 = 1 - 9e-14 came
+// back 4.5e-14 = 405 u off: 316 Y u on the float32 set, whose Y is 1.27, 1.04 times the bound; the float64
+// set, Y = 1.81, still passed).  2.9e-14 and not the 2^-45 beside it: a constant with both
+// words set, as 1e-13 was, leaves every kernel's instruction sequence what it was (a zero low word
+// changed the register allocation and the schedule of k_run and k_live).
+constexpr double kNormSnap = 2.9e-14;
 __device__ __forceinline__ double state_norm2(const double *x) {
     const double n2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3];
-    return fabs(n2 - 1.0) < 1e-13 ? 1.0 : n2;
+    return fabs(n2 - 1.0) < kNormSnap ? 1.0 : n2;
 }
 
 // a * b - c as one three-address v_fma_f64 with a negated operand.  Left to itself the compiler
