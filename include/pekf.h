@@ -439,6 +439,36 @@ int pekf_live_join_noise_dev(int64_t batch, int64_t n_events, const void *ev_pla
                              int32_t *counts, double *refs, uint32_t flags, void *state, double *traj,
                              double *traj_dt, int64_t traj_rows, int *dev_error, void *stream);
 
+/* pekf_live_resume_dev and pekf_live_join_dev handing out the records they apply: what the server writes into
+ * its log beside each X_k (KalmanFilter::WriteTextFile, KFS/KalmanFilter.cpp: the `gyro`, `Acc_1` and `Mag_1`
+ * lines and the dt between two `T` lines), per record of Parser::ExecuteKalmanFilter (KFS/Parser.cpp:248-267).
+ * The b-th filter's r-th record of the call (r < traj_rows, the row of its pose in traj) is stored in three
+ * filter-minor planes of traj_rows rows, exactly pekf_run_rec64_dev's input layout:
+ *   rec_gd [traj_rows][batch] double4 {gyro xyz, dt_ns}   (32-byte aligned)
+ *   rec_am [traj_rows][batch] double4 {acc xyz, mag x}    (32-byte aligned)
+ *   rec_my [traj_rows][batch] double2 {mag y, mag z}      (16-byte aligned)
+ * The values are the doubles the filter step was handed: the low-pass acc / mag, the gyro (f32 events: the
+ * float32 sample widened) and the dt it was applied with, traj_dt's double (a pause of 2^31 ns or more too).  So
+ * pekf_run_rec64_dev with counts over a session's concatenated rows repeats the session, and
+ * pekf_gyro_chain_rec64_dev / pekf_wahba_stream_rec64_dev give the log's q_gyro / Wahba_quart lines.  Nothing
+ * else is written: rows >= counts[b], every row of a filter that is not ready or has not joined.
+ *   noise: NULL -- the launch's q and r, as the parents; otherwise the {q, r} plane of the _noise_dev entries
+ * (16-byte aligned; q and r are then ignored).  Records do not depend on the noise.
+ *   Refused (PEKF_ERR_INVALID) before any device call: traj_rows == 0 or a null traj / traj_dt (a record comes
+ * beside its pose), a null or misaligned record plane, PEKF_EV_F32_RECORDS, and for the join entry any flags but
+ * PEKF_EV_F64_EVENTS.  Every other check, batch == 0 and n_events == 0 as the parents'.  Every output the parents
+ * write has the bits they give it. */
+int pekf_live_resume_rec_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                             const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
+                             const double *noise, int32_t *counts, double *refs, uint32_t flags, void *state,
+                             int resume, double *traj, double *traj_dt, int64_t traj_rows, void *rec_gd,
+                             void *rec_am, void *rec_my, int *dev_error, void *stream);
+int pekf_live_join_rec_dev(int64_t batch, int64_t n_events, const void *ev_planes, const double *init,
+                           const int64_t *t_init, double alpha, double *X, double *P, double q, double r,
+                           const double *noise, int32_t *counts, double *refs, uint32_t flags, void *state,
+                           double *traj, double *traj_dt, int64_t traj_rows, void *rec_gd, void *rec_am,
+                           void *rec_my, int *dev_error, void *stream);
+
 /* Phase 2 of the server's Parser (KFS/Parser.cpp:36-58,84-140; KFS/InitialValues.cpp) on the device: per
  * filter, the mean and sample variance of the first n_avg (the server: 100) samples of each sensor type,
  * and the time phase 3 continues from.  Events as for pekf_frontend_dev (ev_planes [n_events][batch], word

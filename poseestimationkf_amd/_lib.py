@@ -144,6 +144,10 @@ SIGNATURES = {
                                    _i64, _vp, _vp],
     "pekf_live_join_noise_dev": [_i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _i64,
                                  _vp, _vp],
+    "pekf_live_resume_rec_dev": [_i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _u32, _vp, _int,
+                                 _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "pekf_live_join_rec_dev": [_i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _u32, _vp, _vp,
+                               _vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "pekf_frontend_init_resume_dev": [_i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _u32, _vp, _int, _vp],
     "pekf_frontend_init_state_bytes": [_i64, _u32],
     "pekf_session_recycle_dev": [_i64, _i64, _vp, _u32] + [_vp] * 8 + [_vp] * 6 + [_vp, _int, _vp, _vp, _vp] + [_vp],

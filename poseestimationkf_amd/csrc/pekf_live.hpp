@@ -1,7 +1,7 @@
 // pekf_live.hpp -- k_live, the fused front-end + filter kernel, and its record queue (see pekf_live.hip,
 // which instantiates the kernels without trajectory output; pekf_live_traj.hip instantiates their TRAJ twins,
 // pekf_live_resume.hip the resumable kernels of a session fed in chunks, pekf_live_join.hip those whose filters
-// join the session one by one).  The host side every pekf_live_* entry shares closes the file: LiveCall (the
+// join the session one by one, pekf_live_rec.hip those that hand out their records).  The host side every pekf_live_* entry shares closes the file: LiveCall (the
 // entries' common arguments), their checks, and the one launcher, launch_k_live<TRAJ, RESUME, JOIN>.
 #pragma once
 #include "pekf_phase3.hpp"
@@ -316,6 +316,18 @@ struct LiveState {
     }
 };
 
+// Where a REC kernel (k_live<..., REC>) leaves the records it applies: three filter-minor planes [row][batch] in
+// pekf_run_rec64_dev's layout (RecordWindow64's) -- gd double4 {gx, gy, gz, dt_ns}, am double4 {ax, ay, az, mx},
+// my double2 {my, mz}.  Without REC the argument is empty, as NoiseR is without a plane (pekf_step.hpp), so the
+// other kernels' argument block, and with it their code, is what it was.
+struct NoRecArg {};
+struct RecPlanesArg {
+    double4 *gd, *am;
+    double2 *my;
+};
+template <bool REC>
+using RecPlanes = std::conditional_t<REC, RecPlanesArg, NoRecArg>;
+
 // TE: the event planes may hold time events (Phase3::event).  R64: records keep their FP64 acc / mag
 // (SlotsLpf); otherwise they are the f32 stream records pekf_frontend_dev writes (SlotsF32).
 // EV64: FP64 events (PEKF_EV_F64_EVENTS, double4 planes: the server's own sample values), records all
@@ -344,15 +356,21 @@ struct LiveState {
 // NOISE (with RESUME; pekf_live_resume_noise.hip, pekf_live_join_noise.hip): per-filter noise, the lane's own q
 // and r from the {q, r} plane (NoiseQ, pekf_step.hpp) in place of the launch's.  The session state holds the
 // covariance as N, P = rI + sqrt(2) r D N D, so a lane's r must stay what it was for as long as its session lasts.
+// REC (with TRAJ and RESUME; pekf_live_rec.hip, pekf_live_rec_noise.hip): the record each pose came from, the
+// server's log lines gyro / Acc_1 / Mag_1 and the dt between its T lines (KalmanFilter::WriteTextFile).  The lane's
+// r-th record of the launch (r < traj_rows, the pose's row) leaves the doubles handed to ekf_record_step in
+// rec.gd / rec.am / rec.my [r][b] -- an f32-event record's f32 gyro widened, its dt the double take_dt returned
+// (an escaped one too); an FP64-event record's slot as it is -- stored before the step, so nothing more is live
+// across it: five 16-byte stores, into the lane's own row as the pose's are.  Nothing else is written.
 template <bool TE, bool R64, bool EV64 = false, bool TRAJ = false, bool RESUME = false, bool JOIN = false,
-          bool NOISE = false>
+          bool NOISE = false, bool REC = false>
 __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 ? PEKF_LIVE_EV64_WAVES : 2))) void k_live(
     int64_t batch, int64_t n_events, const std::conditional_t<EV64, double4, float4> *__restrict__ ev,
     const double *__restrict__ init, const int64_t *__restrict__ t_init, double alpha, NoiseQ<NOISE> q_arg,
     NoiseR<NOISE> r_arg,
     double *__restrict__ Xio, double *__restrict__ Pio, int32_t *__restrict__ counts, double *__restrict__ refs,
     double *__restrict__ traj, double *__restrict__ traj_dt, int32_t traj_rows, void *__restrict__ state,
-    int32_t resume) {
+    int32_t resume, RecPlanes<REC> rec) {
     using EvT = std::conditional_t<EV64, double4, float4>;
     constexpr int kRing = EV64 ? PEKF_LIVE_RING64 : PEKF_LIVE_RING, kFlush = 3, kQuorum = PEKF_LIVE_QUORUM;
     constexpr int kQueue = EV64 ? PEKF_LIVE_QUEUE_EV64 : R64 ? PEKF_LIVE_QUEUE64 : PEKF_LIVE_QUEUE;
@@ -365,6 +383,7 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
     static_assert(!R64 || kPush == 1, "SlotsLpf's single escaped-dt register needs one record per lane per block");
     static_assert(!JOIN || (RESUME && EV64), "lanes join a resumable session of FP64 events (absolute times)");
     static_assert(!NOISE || (RESUME && (EV64 || R64)), "per-filter noise: the resumable and the joining kernels");
+    static_assert(!REC || (TRAJ && RESUME), "records are exported beside the poses of a resumable or joining launch");
     const int64_t b = (int64_t)blockIdx.x * kRunBlock + threadIdx.x;
     if (b >= batch) return;
     double qs, rs;
@@ -429,6 +448,18 @@ __global__ __launch_bounds__(kRunBlock) __attribute__((amdgpu_waves_per_eu(EV64 
             Queue::unpack(cur, gy, acc, mag);
             bool first = applied == 0;
             if constexpr (RESUME) first = first && fresh;
+            if constexpr (REC) {
+                if (applied < traj_rows) {
+                    const int64_t row = (int64_t)applied * batch + b;
+                    double2 *g = reinterpret_cast<double2 *>(rec.gd) + 2 * row;
+                    double2 *a = reinterpret_cast<double2 *>(rec.am) + 2 * row;
+                    g[0] = make_double2(gy[0], gy[1]);
+                    g[1] = make_double2(gy[2], dt);
+                    a[0] = make_double2(acc[0], acc[1]);
+                    a[1] = make_double2(acc[2], mag[0]);
+                    rec.my[row] = make_double2(mag[1], mag[2]);
+                }
+            }
             if (first)
                 ekf_record_step<kLoopForm>(x, state_norm2(x), P, Wr, kc, gy, dt, false, acc, mag, reload);
             else  // LAZY
@@ -539,6 +570,8 @@ struct LiveCall {
     hipStream_t stream;
     const double *noise = nullptr;  // the pekf_live_*_noise_dev entries: the {q, r} plane, in place of q and r
     bool per_filter = false;        // ... and that the call is one of them
+    // the pekf_live_*_rec_dev entries: the record planes (RecPlanesArg), traj_rows rows each
+    void *rec_gd = nullptr, *rec_am = nullptr, *rec_my = nullptr;
 };
 
 // The argument checks every pekf_live_* entry shares, in two halves: sizes, flags and the trajectory arguments
@@ -577,9 +610,15 @@ static inline int check_live_launch(const LiveCall &c) {
 // Without TRAJ the kernels read none of the trajectory arguments and are handed none.
 // NOISE: the same kernels' per-filter-noise forms (pekf_live_resume_noise.hip, pekf_live_join_noise.hip), handed
 // c.noise where the others are handed c.q and c.r.
-template <bool TRAJ, bool RESUME = false, bool JOIN = false, bool NOISE = false>
+// REC: the TRAJ kernels of a resumable or joining launch that export their records too (pekf_live_rec.hip,
+// pekf_live_rec_noise.hip), handed c.rec_gd / c.rec_am / c.rec_my.
+template <bool TRAJ, bool RESUME = false, bool JOIN = false, bool NOISE = false, bool REC = false>
 int launch_k_live(const LiveCall &c, void *state = nullptr, int32_t resume = 0) {
     static_assert(!NOISE || RESUME, "per-filter noise: the resumable and the joining kernels");
+    static_assert(!REC || (TRAJ && RESUME), "records are exported beside the poses of a resumable or joining launch");
+    RecPlanes<REC> rec;
+    if constexpr (REC)
+        rec = {static_cast<double4 *>(c.rec_gd), static_cast<double4 *>(c.rec_am), static_cast<double2 *>(c.rec_my)};
     const dim3 grid(grid_for(c.batch, kRunBlock)), block(kRunBlock);
     NoiseQ<NOISE> q_arg;
     NoiseR<NOISE> r_arg;
@@ -592,14 +631,14 @@ int launch_k_live(const LiveCall &c, void *state = nullptr, int32_t resume = 0) 
     auto launch = [&](auto kernel, const auto *ev) {
         hipLaunchKernelGGL(kernel, grid, block, 0, c.stream, c.batch, c.n_events, ev, c.init, c.t_init, c.alpha, q_arg,
                            r_arg, c.X, c.P, c.counts, c.refs, TRAJ ? c.traj : nullptr, TRAJ ? c.traj_dt : nullptr,
-                           TRAJ ? (int32_t)c.traj_rows : 0, state, resume);
+                           TRAJ ? (int32_t)c.traj_rows : 0, state, resume, rec);
     };
     if (JOIN || (c.flags & PEKF_EV_F64_EVENTS))  // the one FP64-event variant
-        launch(k_live<false, false, true, TRAJ, RESUME, JOIN, NOISE>, static_cast<const double4 *>(c.ev_planes));
+        launch(k_live<false, false, true, TRAJ, RESUME, JOIN, NOISE, REC>, static_cast<const double4 *>(c.ev_planes));
     else if constexpr (RESUME && !JOIN)
         dispatch_bools(
             [&](auto te) {
-                launch(k_live<te.value, true, false, TRAJ, true, false, NOISE>, static_cast<const float4 *>(c.ev_planes));
+                launch(k_live<te.value, true, false, TRAJ, true, false, NOISE, REC>, static_cast<const float4 *>(c.ev_planes));
             },
             (c.flags & PEKF_EV_TIME_EVENTS) != 0);
     else if constexpr (!RESUME)
@@ -613,5 +652,8 @@ int launch_k_live(const LiveCall &c, void *state = nullptr, int32_t resume = 0) 
 
 // launch_k_live<true> (pekf_live_traj.hip)
 int launch_live_traj(const LiveCall &c);
+
+// launch_k_live<true, true, join, true, true> (pekf_live_rec_noise.hip), for pekf_live_rec.hip's entries
+int launch_live_rec_noise(const LiveCall &c, void *state, int32_t resume, bool join);
 
 }  // namespace pekf

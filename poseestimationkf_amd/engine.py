@@ -535,6 +535,17 @@ class _Trajectory:
         return dict(trajectory=tr, record_dt_ns=dt, record_times_ns=record_times_ns(t_init, dt))
 
 
+def _chunk_records(rows, batch):
+    """The device planes a chunk fed with records=True exports its records into (pekf_live_resume_rec_dev's
+    rec_gd / rec_am / rec_my): a RecordWindow64 of `rows` rows, every byte 0xFF as _Trajectory's buffers, so
+    that what the kernel does not write reads as NaN."""
+    win = RecordWindow64(batch, rows)
+    if rows:
+        for plane in (win.gd, win.am, win.my):
+            check(lib.pekf_memset(plane.ptr, 0xFF, plane.nbytes, None))
+    return win
+
+
 def _scalar_noise_only(filters, what, session):
     """Refuses a per-filter-noise filter in a one-launch session, naming the chunked session to feed instead"""
     if getattr(filters, "noise", None) is not None:
@@ -1123,6 +1134,29 @@ class _ChunkedSession:
     def _first_records(self, first):
         """first (K,) bool: the filters whose first record of the session was applied in this chunk"""
 
+    @staticmethod
+    def _records_trajectory(trajectory, records):
+        """records=True implies a trajectory: without one asked for, the chunk's default row cap (True)"""
+        return True if records and (trajectory is None or trajectory is False) else trajectory
+
+    def _noise_args(self):
+        """(q, r, noise) of a _rec entry: the launch's q and r with a NULL plane, or the filter's {q, r} plane"""
+        f = self.filters
+        return (f.q, f.r, None) if f.noise is None else (0.0, 0.0, f.noise.ptr)
+
+    def _with_records(self, out, win):
+        """Adds "records" to a chunk's trajectory dict: the chunk's RecordWindow64 (_chunk_records, filled by the
+        launch) with the session's refs and counts = min(the chunk's counts, its rows) -- device-resident, as
+        BatchedEKF.run, gyro_chain, wahba_quaternions and download_filters take it.  win.chunk_counts: the chunk's
+        full counts (a filter whose count is above the window's rows had records cut by the row cap)."""
+        counts = out[0]
+        check(lib.pekf_memcpy_d2d(win.refs.ptr, self._refs.ptr, 48 * self.batch, None))
+        check(lib.pekf_device_sync())
+        win.counts = np.minimum(counts, win.window).astype(np.int32)
+        win.chunk_counts = np.array(counts, np.int32)
+        out[-1]["records"] = win
+        return out
+
     def _chunk_result(self, out, counts):
         """The chunk's trajectory dict with record_times_ns continuing from the session's running record time: per
         filter t_init + the running sum of every dt so far, summed in the order one launch's cumsum would.  A
@@ -1228,31 +1262,47 @@ class LiveSession(_ChunkedSession):
             self._book["last_times"] = times[-1].copy()
         return planes, flags
 
-    def feed(self, ev, trajectory=False):
+    def feed(self, ev, trajectory=False, records=False):
         """The next rows of every filter's stream: a synth.generate_events-style dict of types (E, K), values
         (E, K, 3), times (E, K) and optionally values64 (init_* / t_init entries are ignored).  Returns counts
         (K,) int32, the records applied in this chunk, or with trajectory (True or a row cap) (counts, dict of
-        trajectory / record_dt_ns / record_times_ns) as run_events does, rows counted within the chunk."""
+        trajectory / record_dt_ns / record_times_ns) as run_events does, rows counted within the chunk.
+        records=True (pekf_live_resume_rec_dev; it implies trajectory=True where none is asked for, and a row cap
+        holds for poses and records alike): the dict also has "records", the chunk's records as a device-resident
+        RecordWindow64 of that many rows -- what the filter was fed, row for row beside the poses
+        (_ChunkedSession._with_records)."""
         planes, flags = self.pack_chunk(ev)
         buf = DeviceBuffer(planes.nbytes).upload(planes)
-        return self.feed_planes(buf, planes.shape[0], flags, trajectory)
+        return self.feed_planes(buf, planes.shape[0], flags, trajectory, records=records)
 
-    def feed_planes(self, planes, n_events, flags=0, trajectory=False, offset=0):
+    def feed_planes(self, planes, n_events, flags=0, trajectory=False, offset=0, records=False):
         """n_events packed rows ([n_events][K] float4, or double4 for an FP64-event session) of the DeviceBuffer
         `planes`, starting `offset` bytes into it: row ranges of one resident plane are fed without copies.
-        flags: EV_TIME_EVENTS if these rows hold time events (it may differ from chunk to chunk)."""
+        flags: EV_TIME_EVENTS if these rows hold time events (it may differ from chunk to chunk).
+        records: as feed's."""
         K, f = self.batch, self.filters
         n_events, flags = int(n_events), int(flags) | self._form
         self._rows_in(planes, n_events, offset, K * (32 if self._form else 16))
+        trajectory = self._records_trajectory(trajectory, records)
         tj = _Trajectory(chunk_trajectory_rows(trajectory, n_events) if trajectory is True else trajectory, n_events, K)
-        # (a per-filter-noise filter: the same launch with its {q, r} plane in place of q and r)
-        entry, noise = ((lib.pekf_live_resume_dev, (f.q, f.r)) if f.noise is None else
-                        (lib.pekf_live_resume_noise_dev, (f.noise.ptr,)))
-        check(entry(K, n_events, planes.ptr + offset, self._init.ptr, self._t_init.ptr, self.alpha,
-                    f.X.ptr, f.P.ptr, *noise, self._cnt.ptr, self._refs.ptr, flags,
-                    self._state.ptr, int(self._book["started"]), tj.traj.ptr if tj.rows else None,
-                    tj.dt.ptr if tj.rows else None, tj.rows, None, None))
+        win = _chunk_records(tj.rows, K) if records else None
+        if records and tj.rows:   # (no rows: nothing to export, the launch is the one without records)
+            check(lib.pekf_live_resume_rec_dev(K, n_events, planes.ptr + offset, self._init.ptr, self._t_init.ptr,
+                                               self.alpha, f.X.ptr, f.P.ptr, *self._noise_args(), self._cnt.ptr,
+                                               self._refs.ptr, flags, self._state.ptr, int(self._book["started"]),
+                                               tj.traj.ptr, tj.dt.ptr, tj.rows, win.gd.ptr, win.am.ptr, win.my.ptr,
+                                               None, None))
+        else:
+            # (a per-filter-noise filter: the same launch with its {q, r} plane in place of q and r)
+            entry, noise = ((lib.pekf_live_resume_dev, (f.q, f.r)) if f.noise is None else
+                            (lib.pekf_live_resume_noise_dev, (f.noise.ptr,)))
+            check(entry(K, n_events, planes.ptr + offset, self._init.ptr, self._t_init.ptr, self.alpha,
+                        f.X.ptr, f.P.ptr, *noise, self._cnt.ptr, self._refs.ptr, flags,
+                        self._state.ptr, int(self._book["started"]), tj.traj.ptr if tj.rows else None,
+                        tj.dt.ptr if tj.rows else None, tj.rows, None, None))
         out = self._after_launch(tj)
+        if records:
+            out = self._with_records(out, win)
         return out if tj.wanted else out[0]
 
 
@@ -1471,7 +1521,7 @@ class PhoneSession(_ChunkedSession):
         planes = synth.pack_events64(ev, server_event_values(ev))
         return DeviceBuffer(planes.nbytes).upload(planes), shape[0]
 
-    def feed(self, phase2=None, phase3=None, trajectory=False, calibration=None, phase1=None):
+    def feed(self, phase2=None, phase3=None, trajectory=False, calibration=None, phase1=None, records=False):
         """The next rows of the phase-2 plane and of the phase-3 plane: each a dict of types (E, K), values
         (E, K, 3), times (E, K) and optionally values64, synth.EV_NONE where a phone has no message in a row;
         either may be None or have no rows, and the two need not have the same number.  calibration:
@@ -1480,36 +1530,40 @@ class PhoneSession(_ChunkedSession):
         phase 2's state after it), and with trajectory (True or a row cap) a third value, the dict of trajectory /
         record_dt_ns / record_times_ns as LiveSession.feed's, rows counted within the chunk.
         phase1 (a session with n_cal only, which takes no calibration): the chunk's rows of the phase-1 plane, a
-        dict of the same form; every message in it is a calibration sample, whatever its type."""
+        dict of the same form; every message in it is a calibration sample, whatever its type.
+        records=True (pekf_live_join_rec_dev): as LiveSession.feed's -- it implies a trajectory, and the dict gains
+        "records", the chunk's RecordWindow64; in a calibrating session the corrected records, the server's Mag_1."""
         self._check_phase1(calibration, phase1 is not None)
         b1, E1 = self._pack(phase1, "phase1")
         b2, E2 = self._pack(phase2, "phase2")
         b3, E3 = self._pack(phase3, "phase3")
         return self._launch(b2.ptr if E2 else None, E2, b3.ptr if E3 else None, E3, trajectory, calibration,
-                            b1.ptr if E1 else None, E1)
+                            b1.ptr if E1 else None, E1, records=records)
 
     def feed_planes(self, planes2, n2, planes3, n3, trajectory=False, calibration=None, offset2=0, offset3=0,
-                    planes1=None, n1=0, offset1=0):
+                    planes1=None, n1=0, offset1=0, records=False):
         """Row ranges of resident FP64 event planes ([rows][K] double4 DeviceBuffers), without copies: n2 rows of
         planes2 from byte offset2, n3 rows of planes3 from offset3 (offsets as LiveSession.feed_planes': inside the
         buffer, multiples of 16).  A buffer whose row count is 0 may be None.  calibration corrects the rows in
         place, so feed a row once.  planes1 / n1 / offset1 (a session with n_cal only): the chunk's rows of the
-        phase-1 plane, in the same way; the session's own calibration corrects planes2 / planes3 in place too."""
+        phase-1 plane, in the same way; the session's own calibration corrects planes2 / planes3 in place too.
+        records: as feed's."""
         self._check_phase1(calibration, planes1 is not None or int(n1) != 0)
         ptrs = []
         for planes, n, offset in ((planes2, int(n2), int(offset2)), (planes3, int(n3), int(offset3)),
                                   (planes1, int(n1), int(offset1))):
             self._rows_in(planes, n, offset, 32 * self.batch)
             ptrs.append(planes.ptr + offset if n else None)
-        return self._launch(ptrs[0], int(n2), ptrs[1], int(n3), trajectory, calibration, ptrs[2], int(n1))
+        return self._launch(ptrs[0], int(n2), ptrs[1], int(n3), trajectory, calibration, ptrs[2], int(n1),
+                            records=records)
 
-    def feed_frames(self, frames_chunk, calibration=None, trajectory=False):
+    def feed_frames(self, frames_chunk, calibration=None, trajectory=False, records=False):
         """The next [F][K][100] wire frames of the phones (wire.frames): parsed with a row per frame
         (wire_events(..., frame_rows=True): a frame's parse does not depend on earlier frames, and row f of each
         plane is frame f's message of that phase), then fed as feed_planes.  calibration: a dict, as feed;
         "frames" is refused -- without n_cal phase 1 is not chunked: calibrate first (calibrate_magnetometer), or
         construct the session with n_cal=, which then parses the chunk's phase-1 messages too
-        (wire_events(..., phase1=True)) and feeds ev1's first E1 rows."""
+        (wire_events(..., phase1=True)) and feeds ev1's first E1 rows.  records: as feed's."""
         if isinstance(calibration, str) and self._phase1 is None:
             raise ValueError("a chunked session takes calibrate_magnetometer's dict: phase 1 from the frames "
                              "(calibration='frames') is not chunked in this session -- construct the session with "
@@ -1519,16 +1573,17 @@ class PhoneSession(_ChunkedSession):
         if Kf != self.batch:
             raise ValueError("the frames are of %d phones, the session of %d" % (Kf, self.batch))
         if F == 0:
-            return self._launch(None, 0, None, 0, trajectory, calibration)
+            return self._launch(None, 0, None, 0, trajectory, calibration, records=records)
         if self._phase1 is not None:
             w = wire_events(frames_chunk, None, True, phase1=True)
             return self.feed_planes(w["ev2"], w["E2"], w["ev3"], w["E3"], trajectory, None,
-                                    offset3=32 * self.batch * w["ev3_from"], planes1=w["ev1"], n1=w["E1"])
+                                    offset3=32 * self.batch * w["ev3_from"], planes1=w["ev1"], n1=w["E1"],
+                                    records=records)
         w = wire_events(frames_chunk, None, True)
         return self.feed_planes(w["ev2"], w["E2"], w["ev3"], w["E3"], trajectory, calibration,
-                                offset3=32 * self.batch * w["ev3_from"])
+                                offset3=32 * self.batch * w["ev3_from"], records=records)
 
-    def _launch(self, ev2, E2, ev3, E3, trajectory, calibration, ev1=None, E1=0):
+    def _launch(self, ev2, E2, ev3, E3, trajectory, calibration, ev1=None, E1=0, records=False):
         K, f = self.batch, self.filters
         if self._phase1 is not None:   # the chunk's phase-1 rows first: its other rows are corrected with the result
             if E1 or not self._book["started"]:
@@ -1543,15 +1598,25 @@ class PhoneSession(_ChunkedSession):
         check(lib.pekf_frontend_init_resume_dev(K, E2, ev2, self._t_start.ptr, self.n_avg, self._init.ptr,
                                                 self._t_init.ptr, self._ready.ptr, EV_F64_EVENTS, self._p2state.ptr,
                                                 int(self._book["started"]), None))
+        trajectory = self._records_trajectory(trajectory, records)
         tj = _Trajectory(chunk_trajectory_rows(trajectory, E3) if trajectory is True else trajectory, E3, K)
+        win = _chunk_records(tj.rows, K) if records else None
         # (no rows: any valid pointer, none is read)
-        entry, noise = ((lib.pekf_live_join_dev, (f.q, f.r)) if f.noise is None else
-                        (lib.pekf_live_join_noise_dev, (f.noise.ptr,)))   # (per-filter noise: its {q, r} plane)
-        check(entry(K, E3, ev3 if E3 else self._state.ptr, self._init.ptr, self._t_init.ptr,
-                    self.alpha, f.X.ptr, f.P.ptr, *noise, self._cnt.ptr, self._refs.ptr,
-                    EV_F64_EVENTS, self._state.ptr, tj.traj.ptr if tj.rows else None,
-                    tj.dt.ptr if tj.rows else None, tj.rows, None, None))
+        if records and tj.rows:   # (no trajectory rows: nothing to export, the launch is the one without records)
+            check(lib.pekf_live_join_rec_dev(K, E3, ev3 if E3 else self._state.ptr, self._init.ptr, self._t_init.ptr,
+                                             self.alpha, f.X.ptr, f.P.ptr, *self._noise_args(), self._cnt.ptr,
+                                             self._refs.ptr, EV_F64_EVENTS, self._state.ptr, tj.traj.ptr, tj.dt.ptr,
+                                             tj.rows, win.gd.ptr, win.am.ptr, win.my.ptr, None, None))
+        else:
+            entry, noise = ((lib.pekf_live_join_dev, (f.q, f.r)) if f.noise is None else
+                            (lib.pekf_live_join_noise_dev, (f.noise.ptr,)))   # (per-filter noise: its {q, r} plane)
+            check(entry(K, E3, ev3 if E3 else self._state.ptr, self._init.ptr, self._t_init.ptr,
+                        self.alpha, f.X.ptr, f.P.ptr, *noise, self._cnt.ptr, self._refs.ptr,
+                        EV_F64_EVENTS, self._state.ptr, tj.traj.ptr if tj.rows else None,
+                        tj.dt.ptr if tj.rows else None, tj.rows, None, None))
         out = self._after_launch(tj)
+        if records:
+            out = self._with_records(out, win)
         return out[:1] + (self._ready.download((K,), np.int32).astype(bool),) + out[1:]
 
     def _first_records(self, first):
@@ -1700,6 +1765,60 @@ class PhoneSession(_ChunkedSession):
         if len(np.intersect1d(src, dst)):
             raise ValueError("src and dst overlap: a phone moves into a free column (no permutation in place)")
         self.import_columns(dst, self.export_columns(src))
+
+
+class SessionLog:
+    """The server's log (KalmanFilter::WriteTextFile, logformat's format) of the listed columns of a chunked
+    session, written chunk by chunk from the chunks fed with records=True: the replayable trace main_file.py runs
+    from, byte for byte logformat.write_log of the whole session's arrays.
+
+    session: a LiveSession or PhoneSession; columns: distinct column indices (recycle's rule); paths: a file per
+    column.  append(result) takes a chunk's returned dict (the last value feed / feed_planes / feed_frames
+    return).  A column's header -- mag_0 / acc_0 from the session's refs, the three identity lines, and the
+    phone's t_init as the T before its first record's T -- is written when its first record arrives, so a phone
+    with no record gets no file; then per record gyro, T (record_times_ns), q_gyro (records.gyro_chain from the
+    column's own q_gyro of its last record so far: the identity at first, then row count - 1 of the previous
+    chunk -- not the kernel's final value, which has run over rows the chunk did not write), Mag_1, Acc_1, X_k
+    (the chunk's trajectory row) and Wahba_quart (records.wahba_quaternions(), main_file.py:40's 0.5 / 0.5).
+    Every chunk in which a listed column applies a record must be appended, in order; a column that is recycled
+    or moved starts another phone's log: make a new SessionLog for it."""
+
+    def __init__(self, session, columns, paths):
+        self.session, self.columns = session, _recycle_columns(columns, session.batch)
+        self.paths = [os.fspath(p) for p in paths]
+        if len(self.paths) != len(self.columns):
+            raise ValueError("%d paths for %d columns" % (len(self.paths), len(self.columns)))
+        self._q = np.tile([1.0, 0.0, 0.0, 0.0], (session.batch, 1))
+        self._begun = np.zeros(len(self.columns), bool)
+
+    def append(self, result):
+        from . import logformat
+        cols = self.columns
+        win = result.get("records") if isinstance(result, dict) else None
+        if win is None:
+            raise ValueError("SessionLog.append takes the dict of a chunk fed with records=True (a chunk fed without "
+                             "records cannot be logged, and the record times are NaN from there on)")
+        if (np.asarray(win.chunk_counts)[cols] > win.window).any():
+            raise ValueError("the chunk's row cap (%d rows) cut a listed column's records: they were applied but "
+                             "not exported, and the record times are NaN from there on" % win.window)
+        counts = np.asarray(win.counts)
+        if len(cols) == 0 or win.window == 0 or not counts[cols].any():
+            return
+        wahba = win.wahba_quaternions()
+        q_gyro = win.gyro_chain(self._q, want_traj=True)[1]
+        gyro, _, acc, mag, refs = win.download_filters(cols)
+        t_init = self.session._book["t_init"]
+        for i, k in enumerate(cols):
+            n = int(counts[k])
+            if n == 0:
+                continue
+            times = [t_init[k]] * (not self._begun[i]) + list(result["record_times_ns"][:n, k])
+            with open(self.paths[i], "a" if self._begun[i] else "w") as fh:
+                logformat.write_log(fh, times, gyro[:n, i], acc[:n, i], mag[:n, i], refs[i, :3], refs[i, 3:],
+                                    q_gyro[:n, k], result["trajectory"][:n, k], wahba[:n, k],
+                                    continued=bool(self._begun[i]))
+            self._begun[i] = True
+            self._q[k] = q_gyro[n - 1, k]
 
 
 class FilterHandle:

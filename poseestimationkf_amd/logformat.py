@@ -39,13 +39,17 @@ def _vec(v):
     return ",".join("%f" % float(x) for x in v)
 
 
-def write_log(fh, timestamps, gyro, acc, mag, acc0, mag0, q_gyro=None, x_k=None, wahba=None):
+def write_log(fh, timestamps, gyro, acc, mag, acc0, mag0, q_gyro=None, x_k=None, wahba=None, continued=False):
     """Write a single-filter trace in the server's log format.
 
     timestamps: n+1 absolute ns values (T0 then one per step); gyro/acc/mag: (n,3);
     q_gyro / x_k / wahba: optional (n,4) side channels (written as zeros when absent).
+    continued: the next n steps of a trace whose earlier steps are already written (engine.SessionLog) -- no
+    header lines and no previousT line, and timestamps holds the n step values alone.
     """
     n = len(gyro)
+    if continued:
+        timestamps = [None] + list(timestamps)
     assert len(timestamps) == n + 1
     zeros = np.zeros((n, 4))
     q_gyro = zeros if q_gyro is None else q_gyro
@@ -53,14 +57,15 @@ def write_log(fh, timestamps, gyro, acc, mag, acc0, mag0, q_gyro=None, x_k=None,
     wahba = zeros if wahba is None else wahba
     out = fh if hasattr(fh, "write") else open(fh, "w")
     try:
-        out.write("mag_0 : %s\n" % _vec(mag0))
-        out.write("acc_0 : %s\n" % _vec(acc0))
-        out.write("q_gyro : 1.0, 0.0, 0.0, 0.0\n")
-        out.write("X_k : 1.0, 0.0, 0.0, 0.0\n")
-        out.write("Wahba_quart : 1.0, 0.0, 0.0, 0.0\n")
+        if not continued:
+            out.write("mag_0 : %s\n" % _vec(mag0))
+            out.write("acc_0 : %s\n" % _vec(acc0))
+            out.write("q_gyro : 1.0, 0.0, 0.0, 0.0\n")
+            out.write("X_k : 1.0, 0.0, 0.0, 0.0\n")
+            out.write("Wahba_quart : 1.0, 0.0, 0.0, 0.0\n")
         for i in range(n):
             out.write("gyro : %s\n" % _vec(gyro[i]))
-            if i == 0:
+            if i == 0 and not continued:
                 out.write("T : %d\n" % int(timestamps[0]))
             out.write("T : %d\n" % int(timestamps[i + 1]))
             out.write("q_gyro : %s\n" % _vec(q_gyro[i]))
