@@ -699,6 +699,51 @@ int pekf_wire_events_p1_dev(int64_t batch, int64_t n_frames, const void *frames,
                             int32_t *n2, int32_t *n3, int32_t *bad_frame, int *dev_error, int32_t *row_bounds,
                             uint32_t flags, void *stream);
 
+/* A refused frame is its phone's business (the server: one process per client, KFS/Server.cpp:58,93; a frame in
+ * a form std::stod reads is parsed like any other, one std::stod / std::stoll throws on ends that client's
+ * process alone, since no file of KFS/ has a try).  The two entries below let the host take over exactly the
+ * phones pekf_wire_events_*_dev stopped (bad_frame[b] >= 0) and leave every other column alone:
+ * pekf_wire_parse_frames reads their frames between the two calls.
+ *
+ * pekf_wire_gather_frames_dev: the frames [frame0, n_frames) of the n_cols columns listed in cols (device int32)
+ * out of frames ([n_frames][batch][100], device, 4-byte aligned) into out ([n_cols][n_frames - frame0][100],
+ * device, 4-byte aligned): one download then brings the listed phones' frames, and nobody else's.  A listed
+ * column outside [0, batch) gives frames of NULs (no message). */
+int pekf_wire_gather_frames_dev(int64_t batch, int64_t n_frames, const void *frames, int64_t n_cols,
+                                const int32_t *cols, int64_t frame0, void *out, void *stream);
+/* pekf_wire_patch_dev: host-built event cells into the listed columns of the planes, one launch for all of them.
+ * cols: n_cols records in HOST memory, which the entry checks before anything is launched, and cols_dev: the same
+ * records in device memory (8-byte aligned; the caller's upload, ordered before this call on the stream), which the
+ * kernel reads -- the entry itself allocates, copies and waits for nothing: record i names its column, and per plane p (0: ev1, 1: ev2, 2: ev3) the
+ * first row it rewrites, from_row[p], and the cells it has for it, n_cells[p].  cells (device, 16-byte aligned;
+ * may be NULL if cell_rows == 0): [3][cell_rows][n_cols] double4 in PEKF_EV_F64_EVENTS' form {x, y, z, bits(t) |
+ * type} (type 3 for a Type no sensor takes; a phase-1 time the event cannot hold stored as 0, as
+ * pekf_wire_events_p1_dev does) -- lane-minor, so adjacent records load adjacent cells, and adjacent columns
+ * store adjacent ones.  Column col's row from_row[p] + j of plane p becomes cells[p][j][i] for j < n_cells[p]
+ * and the no-message event for every row after those below the plane's e_max; no row at or above e_max, no row
+ * below from_row[p] and no column that is not listed is written (n_cells = {0, 0, 0}: the column holds no message
+ * from from_row on).  n1 / n2 / n3[col] = n[0..2], first_t2[col] and bad_frame[col] (may be NULL) are set from
+ * the record.  ev1 / n1 NULL: no phase-1 plane (pekf_wire_events_ext_dev's planes), plane 0 of the cells unread.
+ * row_bounds (device, 3 int32, or NULL): when given, pekf_wire_events_*_dev's row bounds are computed afresh from
+ * the patched planes' first n_rows rows, exactly (a second kernel reads every cell's last word): [0], [1] as
+ * PEKF_WIRE_FRAME_ROWS states them with n_rows for n_frames, [2] for ev1 (0 without it).
+ * PEKF_ERR_INVALID, before any launch: negative sizes, misaligned planes or cells, a column outside [0, batch),
+ * a negative from_row or n_cells, n_cells above cell_rows, n_rows above an e_max.  n_cols == 0 without
+ * row_bounds: nothing is launched. */
+typedef struct {
+    int32_t col;          /* the column, in [0, batch) */
+    int32_t bad_frame;    /* -1, or the frame that stopped the phone for good */
+    int32_t n[3];         /* its messages of phases 1, 2, 3 */
+    int32_t from_row[3];  /* per plane: the first row rewritten */
+    int32_t n_cells[3];   /* per plane: cells given, rows from_row .. from_row + n_cells - 1 */
+    int32_t reserved;     /* 0 */
+    int64_t first_t2;     /* the time of its first phase-2 message (0: none) */
+} pekf_wire_patch_col;
+int pekf_wire_patch_dev(int64_t batch, int64_t n_cols, const pekf_wire_patch_col *cols,
+                        const pekf_wire_patch_col *cols_dev, int64_t cell_rows, const void *cells, int64_t e1_max, int64_t e2_max, int64_t e3_max, void *ev1, void *ev2,
+                        void *ev3, int64_t *first_t2, int32_t *n1, int32_t *n2, int32_t *n3, int32_t *bad_frame,
+                        int64_t n_rows, int32_t *row_bounds, void *stream);
+
 /* ---------------- the phone -> server wire: host code ----------------
  * The Android client sends each sample as text, Float.toString of each value
  * (ASC/MessageSender.java:217-233: "#<phase>,<type>:<x>,<y>,<z>,t:<ns>" padded to 99 characters), and
@@ -711,6 +756,23 @@ int pekf_wire_events_p1_dev(int64_t batch, int64_t n_frames, const void *frames,
  * stoll would throw on returns PEKF_ERR_INVALID naming its line. */
 int pekf_wire_parse(const char *text, int64_t len, int64_t max_events, uint8_t *phase, uint8_t *type, double *xyz,
                     int64_t *t_ns, int64_t *n_events);
+/* The same parse frame by frame, as the server's recv loop takes its input (KFS/Server.cpp:35,84: recv of
+ * messageSize = 100 bytes; :97: the message is std::string(buf, 0, n) of a char *buf, cut at the first NUL;
+ * Parser::run, KFS/Parser.cpp:357-363: kept if it starts with '#'; ProcessString, :12-26: parsed if more than
+ * 30 characters follow).  frames: n_frames x 100 bytes, each one message whatever it holds -- a '\n' inside a
+ * frame does not split it, which pekf_wire_parse's lines cannot express.  Per frame, status[f]:
+ * PEKF_WIRE_NO_HASH (no '#'), PEKF_WIRE_SHORT (30 characters or fewer after the '#'), PEKF_WIRE_THROWS (the
+ * server's std::stod / std::stoll would throw: the reference has no try anywhere, so this frame ends that
+ * client's server process) or PEKF_WIRE_MESSAGE (processed), and for a processed frame phase / type (the
+ * characters' values - '0', as pekf_wire_parse's), xyz[3 f ..] and t_ns[f]; zeros for any other status.  A
+ * frame that throws is reported and the next one read: the call never stops at one. */
+#define PEKF_WIRE_FRAME_BYTES 100
+#define PEKF_WIRE_NO_HASH 0
+#define PEKF_WIRE_SHORT 1
+#define PEKF_WIRE_THROWS 2
+#define PEKF_WIRE_MESSAGE 3
+int pekf_wire_parse_frames(int64_t n_frames, const uint8_t *frames, uint8_t *status, uint8_t *phase, uint8_t *type,
+                           double *xyz, int64_t *t_ns);
 /* out[i] = the double std::stod makes of Float.toString(in[i]): the shortest decimal that rounds to the
  * float, the closest one among those (JDK 19+ Float.toString; one that needs a single digit prints the
  * closest of one or two digits), read back correctly rounded. */

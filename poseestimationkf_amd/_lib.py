@@ -131,6 +131,10 @@ SIGNATURES = {
     "pekf_wire_events_ext_dev": [_i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "pekf_wire_events_p1_dev": [_i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _u32, _vp],
+    "pekf_wire_parse_frames": [_i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pekf_wire_gather_frames_dev": [_i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    "pekf_wire_patch_dev": [_i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _i64, _vp, _vp],
     "pekf_live_dev": [_i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp],
     "pekf_live_ext_dev": [_i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _dbl, _dbl, _vp, _vp, _u32, _vp, _vp],
     "pekf_live_traj_dev": [_i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _dbl, _dbl, _vp, _vp, _u32, _vp, _vp, _i64, _vp,

@@ -13,6 +13,10 @@
 //    std::string(buf, 0, n) cuts it, Parser::run's '#' test and ProcessString's length test and field
 //    splitting, strtod / strtoll as std::stod / std::stoll call them, strtod in the "C" locale,
 //    pekf_cnum.hpp).
+//  * pekf_wire_parse_frames: the same parse frame by frame, as the server's recv loop takes its input (one
+//    100-byte frame is one message, a '\n' inside it included), with a status per frame; a frame the server's
+//    std::stod / std::stoll would throw on is reported and the next one read -- what the engine's
+//    refused="repair" reads the phones the device parser stopped with (pekf_wire_repair.hip).
 //  * pekf_f32_wire_values: for samples known only as floats, the double the server would parse from
 //    Float.toString(f).  Float.toString prints the shortest decimal that rounds to f, the closest to f
 //    among those (JDK 19+ specification; for a float whose shortest decimal has one digit it picks the
@@ -221,6 +225,40 @@ int pekf_wire_parse(const char *text, int64_t len, int64_t max_events, uint8_t *
         i = end;
     }
     *n_events = n;
+    return PEKF_OK;
+}
+
+int pekf_wire_parse_frames(int64_t n_frames, const uint8_t *frames, uint8_t *status, uint8_t *phase, uint8_t *type,
+                           double *xyz, int64_t *t_ns) {
+    if (n_frames < 0) return pekf::set_error(PEKF_ERR_INVALID, "negative size");
+    if (n_frames > 0 && !(frames && status && phase && type && xyz && t_ns))
+        return pekf::set_error(PEKF_ERR_INVALID, "null pointer");
+    std::string msg;
+    for (int64_t f = 0; f < n_frames; ++f) {
+        // One recv'd frame is one message, whatever bytes it holds (a '\n' among them): cut at its first NUL
+        // (Server.cpp:97), kept if it starts with '#' (Parser::run), parsed if more than 30 characters follow
+        // (ProcessString)
+        const char *fr = reinterpret_cast<const char *>(frames) + f * PEKF_WIRE_FRAME_BYTES;
+        const int64_t len = (int64_t)strnlen(fr, PEKF_WIRE_FRAME_BYTES);
+        Message m = {'0', '0', {0.0, 0.0, 0.0}, 0};
+        int st = PEKF_WIRE_NO_HASH;
+        if (fr[0] == '#') {
+            st = PEKF_WIRE_SHORT;
+            if (len - 1 > 30) {
+                // a frame the server's std::stod / std::stoll would throw on is reported, and the next one read
+                const bool ok = parse_fast(fr + 1, fr + len, m) || parse_general(msg, fr + 1, len - 1, m);
+                st = ok ? PEKF_WIRE_MESSAGE : PEKF_WIRE_THROWS;
+                if (!ok) m = Message{'0', '0', {0.0, 0.0, 0.0}, 0};
+            }
+        }
+        status[f] = (uint8_t)st;
+        phase[f] = (uint8_t)(m.ph - '0');
+        type[f] = (uint8_t)(m.ty - '0');
+        xyz[3 * f] = m.v[0];
+        xyz[3 * f + 1] = m.v[1];
+        xyz[3 * f + 2] = m.v[2];
+        t_ns[f] = (int64_t)m.t;
+    }
     return PEKF_OK;
 }
 

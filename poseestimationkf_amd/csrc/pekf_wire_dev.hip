@@ -30,7 +30,8 @@
 // "NaN", "Infinity" and "-Infinity" are Float.toString's non-finite forms.  A frame in any other form
 // (a number strtod would read but the client never prints: blanks, hex, more than 19 digits; or text
 // std::stod / std::stoll would throw on) is not parsed here: the phone's first such frame is reported
-// (bad_frame, *dev_error bit 1) and pekf_wire_parse on the host takes it.
+// (bad_frame, *dev_error bit 1) and stops that phone alone; the host reads its frames from there on
+// (pekf_wire_parse_frames) and writes them into its column (pekf_wire_patch_dev, pekf_wire_repair.hip).
 #include "pekf_internal.hpp"
 #include "pekf_phase3.hpp"
 

@@ -627,7 +627,130 @@ def _frames_shape(frames):
     return int(shape[0]), int(shape[1])
 
 
-def wire_events(frames, stream=None, frame_rows=False, phase1=False):
+REFUSED_MODES = ("raise", "repair")
+
+
+def _check_refused(refused):
+    if refused not in REFUSED_MODES:
+        raise ValueError("refused must be 'raise' or 'repair', not %r" % (refused,))
+
+
+# pekf_wire_patch_col (include/pekf.h): one record per patched column
+_PATCH_COL = np.dtype([("col", np.int32), ("bad_frame", np.int32), ("n", np.int32, 3), ("from_row", np.int32, 3),
+                       ("n_cells", np.int32, 3), ("reserved", np.int32), ("first_t2", np.int64)])
+assert _PATCH_COL.itemsize == 56
+_EV64_TIME_LIMIT = 2.0 ** 51   # ns: what an FP64 event's time can hold (pekf_wire_dev.hip, take())
+
+
+def _refused_frames(frames, F, K, cols, f0, stream):
+    """The frames [f0, F) of the columns cols as (len(cols), F - f0, 100) uint8 on the host: a slice of a host
+    array; for a device triple one gather launch (pekf_wire_gather_frames_dev) and one download of those frames."""
+    n, nf = len(cols), F - f0
+    if not isinstance(frames, tuple):
+        return np.ascontiguousarray(np.asarray(frames, np.uint8)[f0:, cols].transpose(1, 0, 2))
+    if n == 0 or nf == 0:
+        return np.zeros((n, nf, 100), np.uint8)
+    dcols = DeviceBuffer(4 * n).upload(np.ascontiguousarray(cols, np.int32), stream)
+    out = DeviceBuffer(100 * n * nf)
+    check(lib.pekf_wire_gather_frames_dev(K, F, frames[0].ptr, n, dcols.ptr, f0, out.ptr, stream))
+    return out.download((n, nf, 100), np.uint8, stream)
+
+
+def _repair_wire(w, dev, frames, F, K, stream, frame_rows, phase1, bad, bounds, dead):
+    """wire_events' repair: the host takes over the phones the device parser stopped (bad (K,) >= 0) and blanks the
+    columns of `dead` ((K,) bool or None: a session's phones that stopped in an earlier chunk).  The refused phones'
+    frames from their bad_frame on are read by wire.parse_frames and walked as the kernel walks them (take(),
+    pekf_wire_dev.hip): a frame the server skips is no message; a processed one is a message of its phase's plane
+    (phases other than 1 / 2 / 3, or phase 1 without its plane, are skipped; a phase-1 time the event cannot hold
+    is stored as 0); a frame the server's std::stod / std::stoll throw on, or a phase-2 / phase-3 time of 2^51 ns
+    or more, stops the phone for good.  One pekf_wire_patch_dev launch writes the columns (dev: the parse's n1 /
+    n2 / n3 / bad_frame DeviceBuffers, n1's None without phase 1); w's counts and row bounds are set afresh.
+    Returns (bad_frame (K,) int32, repaired (K,) bool)."""
+    from . import wire
+    dead = np.zeros(K, bool) if dead is None else dead
+    live = np.nonzero((bad >= 0) & ~dead)[0]
+    cols = np.concatenate([live, np.nonzero(dead)[0]]).astype(np.int32)
+    planes = ((1, 2, 3) if phase1 else (2, 3))
+    counts = {1: w.get("n1"), 2: w["n2"], 3: w["n3"]}
+    first_t2 = w["first_t2"].download((K,), np.int64, stream)
+    rec = np.zeros(len(cols), _PATCH_COL)
+    rec["col"], rec["bad_frame"] = cols, -1
+    out_bad, repaired = np.full(K, -1, np.int32), np.zeros(K, bool)
+    nl = len(live)
+    f0 = int(bad[live].min()) if nl else F
+    fills = []
+    if nl:
+        sub = _refused_frames(frames, F, K, live, f0, stream)
+        p = wire.parse_frames(sub.reshape(-1, 100))
+        st, ph = p["status"].reshape(nl, F - f0), p["phase"].reshape(nl, F - f0)
+        ty, t = p["types"].reshape(nl, F - f0), p["times"].reshape(nl, F - f0)
+        frame = f0 + np.arange(F - f0)[None, :]
+        mine = frame >= bad[live][:, None]                     # the frames the device did not take
+        td = t.astype(np.float64)
+        fits = np.abs(td) < _EV64_TIME_LIMIT
+        stops = mine & ((st == wire.THROWS) | ((st == wire.MESSAGE) & ((ph == 2) | (ph == 3)) & ~fits))
+        stop = np.where(stops.any(axis=1), stops.argmax(axis=1), F - f0)
+        taken = mine & (np.arange(F - f0)[None, :] < stop[:, None])
+        out_bad[live] = np.where(stop < F - f0, f0 + stop, -1)
+        repaired[live] = out_bad[live] != bad[live]
+        rec["bad_frame"][:nl] = out_bad[live]
+        # the events {x, y, z, bits(t) | type}: type 3 for a Type no sensor takes, a phase-1 time out of range as 0
+        cell = np.empty((nl, F - f0, 4), np.uint64)
+        cell[..., :3] = p["values"].reshape(nl, F - f0, 3).view(np.uint64)
+        cell[..., 3] = np.where(fits, td, 0.0).view(np.uint64) | np.where(ty <= 2, ty, 3).astype(np.uint64)
+        for pl in planes:
+            msg = taken & (st == wire.MESSAGE) & (ph == pl)
+            ii, jj = np.nonzero(msg)
+            n_before = counts[pl][live]
+            if frame_rows:   # row f; the rows between the phone's messages are no-message rows
+                from_row = bad[live]
+                at = f0 + jj - from_row[ii]
+                n_cells = np.zeros(nl, np.int64)
+                np.maximum.at(n_cells, ii, at + 1)
+            else:            # the phone's next compacted rows
+                from_row = n_before
+                at = np.cumsum(msg, axis=1)[ii, jj] - 1
+                n_cells = msg.sum(axis=1)
+            rec["from_row"][:nl, pl - 1], rec["n_cells"][:nl, pl - 1] = from_row, n_cells
+            rec["n"][:nl, pl - 1] = n_before + msg.sum(axis=1)
+            if pl == 2:      # t_start: the first phase-2 message's time, if the phone had none before
+                has = msg.any(axis=1) & (n_before == 0)
+                t_first = t[np.arange(nl), msg.argmax(axis=1)]
+                rec["first_t2"][:nl] = np.where(has, t_first, first_t2[live])
+            fills.append((pl - 1, at, ii, cell[ii, jj]))
+    cell_rows = int(rec["n_cells"].max(initial=0))
+    cells = np.zeros((3, cell_rows, len(cols), 4), np.uint64)
+    cells[..., 3] = np.uint64(synth.EV64_NONE_W)
+    for pl, at, ii, e in fills:
+        cells[pl, at, ii] = e
+    cb = DeviceBuffer(max(cells.nbytes, 16))
+    if cells.nbytes:
+        cb.upload(cells, stream)
+    n1b, n2b, n3b, badb = dev
+    ev1, n1p = (w["ev1"].ptr, n1b.ptr) if phase1 else (None, None)
+    rb = DeviceBuffer(max(rec.nbytes, 8))
+    if rec.nbytes:
+        rb.upload(rec, stream)
+    check(lib.pekf_wire_patch_dev(K, len(cols), rec.ctypes.data, rb.ptr, cell_rows, cb.ptr if cell_rows else None,
+                                  F if phase1 else 0, F, F, ev1, w["ev2"].ptr, w["ev3"].ptr, w["first_t2"].ptr, n1p,
+                                  n2b.ptr, n3b.ptr, badb.ptr, F if frame_rows else 0,
+                                  bounds.ptr if frame_rows else None, stream))
+    check(lib.pekf_device_sync() if stream is None else lib.pekf_stream_sync(stream))
+    for pl in planes:
+        counts[pl][cols] = rec["n"][:, pl - 1]
+    if frame_rows:
+        bw = bounds.download((3,), np.int32)
+        E2, E3, E1 = int(bw[0]), int(bw[1]), int(bw[2])
+    else:
+        E2, E3 = int(w["n2"].max(initial=0)), int(w["n3"].max(initial=0))
+        E1 = int(w["n1"].max(initial=0)) if phase1 else 0
+    w.update(E2=E2, E3=E3, ev3_from=F - E3 if frame_rows else 0)
+    if phase1:
+        w["E1"] = E1
+    return out_bad, repaired
+
+
+def wire_events(frames, stream=None, frame_rows=False, phase1=False, refused="raise", stopped=None):
     """The clients' 100-byte wire frames -> FP64 event planes on the device (pekf_wire_events_ext_dev;
     phase1: pekf_wire_events_p1_dev).
 
@@ -641,9 +764,23 @@ def wire_events(frames, stream=None, frame_rows=False, phase1=False):
     phase1: the phase-1 messages too, every one whatever its Type (calibrate_magnetometer's samples) -- the
     dict also has ev1 DeviceBuffer [n_frames][batch] double4, E1 the rows that hold them (ev1's first E1:
     the most phase-1 messages of any phone, or with frame_rows 1 + the last row holding one) and n1
-    (batch,) int32; everything else is as without it, bit for bit.  Raises
+    (batch,) int32; everything else is as without it, bit for bit.
+    refused: what a frame the device parser does not take does.  "raise" (default): raises ValueError
     if a phone's frame is not in the client's form (wire.parse on the host reads any form std::stod
-    does)."""
+    does).  "repair": only that phone is affected, as with the server, which runs a process per client.  The launches
+    are the same; if the error word reports a refused frame, the host reads the refused phones' frames from the
+    earliest refused frame of any of them on
+    (wire.parse_frames; for a device triple after one gather launch and a download of those phones' frames alone)
+    and one patch launch (pekf_wire_patch_dev) writes their columns: a form std::stod reads (blanks, "+1.5", "7",
+    hex, more than 19 digits, "inf") is the message the server parses, bit for bit; a frame its std::stod /
+    std::stoll throw on, or a phase-2 / phase-3 time of 2^51 ns or more, which the event cannot carry, stops that
+    phone there for good -- the reference has no try, so that client's server process ends, and nobody else's.  The
+    dict then also has bad_frame (batch,) int32 -- -1, or the frame that stopped the phone -- and repaired (batch,)
+    bool: the phone had at least one frame taken by the host.
+    stopped ((batch,) bool or None): session plumbing, not a user option -- PhoneSession.feed_frames passes its
+    own mark here: phones whose stream ended before these frames -- their columns
+    are no-message rows whatever the frames hold (the same patch launch, with no cells), their bad_frame is -1."""
+    _check_refused(refused)
     F, K = _frames_shape(frames)
     if isinstance(frames, tuple):
         fb = frames[0]
@@ -665,10 +802,15 @@ def wire_events(frames, stream=None, frame_rows=False, phase1=False):
                                            WIRE_FRAME_ROWS if frame_rows else 0, stream))
     check(lib.pekf_device_sync() if stream is None else lib.pekf_stream_sync(stream))
     n2, n3 = n2b.download((K,), np.int32), n3b.download((K,), np.int32)
+    dead = None if stopped is None or not np.any(stopped) else np.asarray(stopped, bool).reshape(K)
+    bad = None
     if int(errb.download((1,), np.int32)[0]) & 1:
         bad = badb.download((K,), np.int32)
-        k = int(np.argmax(bad >= 0))
-        raise ValueError("phone %d, frame %d: not in the client's message form (wire.parse reads it)" % (k, bad[k]))
+        if dead is not None:   # (a phone whose stream has ended sends nothing that counts)
+            bad = np.where(dead, -1, bad).astype(np.int32)
+        if refused == "raise" and (bad >= 0).any():
+            k = int(np.argmax(bad >= 0))
+            raise ValueError("phone %d, frame %d: not in the client's message form (wire.parse reads it)" % (k, bad[k]))
     n1 = n1b.download((K,), np.int32) if phase1 else None
     if frame_rows:  # the rows that hold messages of any phone: ev2's first E2, ev3's from row F - E3, ev1's first E1
         bw = bounds.download((3 if phase1 else 2,), np.int32)
@@ -680,11 +822,18 @@ def wire_events(frames, stream=None, frame_rows=False, phase1=False):
                first_t2=t2b, frames=fb)
     if phase1:
         out.update(ev1=ev1, E1=E1, n1=n1)
+    bad_frame, repaired = np.full(K, -1, np.int32), np.zeros(K, bool)
+    if F and (dead is not None or (bad is not None and (bad >= 0).any())):   # (refused == "raise": dead columns only)
+        bad_frame, repaired = _repair_wire(out, (n1b if phase1 else None, n2b, n3b, badb), frames, F, K, stream,
+                                           frame_rows, phase1, np.full(K, -1, np.int32) if bad is None else bad,
+                                           bounds, dead)
+    if refused == "repair":
+        out.update(bad_frame=bad_frame, repaired=repaired)
     return out
 
 
 def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_rows=True, calibration=None,
-                     n_cal=100, trajectory=False):
+                     n_cal=100, trajectory=False, refused="raise"):
     """A whole client session from the clients' wire frames, on the device end to end (KFS/Server.cpp's
     recv'd frames -> Parser.cpp:28-72): pekf_wire_events_ext_dev (the server's parse into FP64 event
     planes), pekf_frontend_init_ext_dev (phase 2) and pekf_live_ext_dev (phase 3 + the filter) on the
@@ -700,9 +849,16 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     then also has calibration, the dict calibrate_magnetometer returns.  The only host round trip is
     wire_events' own (the error word and the bounds).  trajectory: as run_session (True: a row per three of
     the phase-3 rows the launch reads), from the same launch, with either kind of rows and any calibration.
+    refused: as wire_events.  "raise" (default): a frame the device parser does not take raises ValueError, for the
+    whole batch.  "repair": only its phone is affected -- the host reads that phone's frames from it on and the
+    session goes on (with no refused frame the launches are the same); the dict gains bad_frame (K,) int32 and
+    repaired (K,) bool, wire_events'.  A stopped phone (bad_frame >= 0: a frame the server's std::stod / std::stoll
+    throw on, which ends that client's server process) is a phone whose stream ended at that frame: it keeps
+    whatever ready, counts and state it had reached.
     Raises ValueError, before anything is launched, if
-    filters.batch is not the frames' phone count or calibration is another string."""
+    filters.batch is not the frames' phone count, calibration is another string or refused an unknown one."""
     K = filters.batch
+    _check_refused(refused)
     _scalar_noise_only(filters, "run_wire_session", "PhoneSession (feed_frames)")
     from_frames = isinstance(calibration, str)
     if from_frames and calibration != "frames":
@@ -710,7 +866,7 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     Kf = _frames_shape(frames)[1]
     if Kf != K:  # the planes' column stride is the frames' phone count: any other batch reads them wrong
         raise ValueError("the frames are of %d phones, the filters of %d" % (Kf, K))
-    w = wire_events(frames, stream, frame_rows, phase1=from_frames)
+    w = wire_events(frames, stream, frame_rows, phase1=from_frames, refused=refused)
     if from_frames:
         calibration = _launch_calibration(K, w["E1"], w["ev1"].ptr, n_cal, EV_F64_EVENTS, stream)
     if calibration is not None:  # with frame rows the no-message rows are walked too (and left as they are)
@@ -720,8 +876,11 @@ def run_wire_session(frames, filters, n_avg=100, alpha=0.1, stream=None, frame_r
     ev3 = w["ev3"]
     if w["ev3_from"]:  # (frame rows) the leading rows no phone has a phase-3 message in
         ev3 = types.SimpleNamespace(ptr=ev3.ptr + 32 * K * w["ev3_from"])
-    return _finish_session(filters, ev3, w["E3"], p2, alpha, EV_F64_EVENTS, trajectory, calibration, stream,
-                           from_frames)
+    out = _finish_session(filters, ev3, w["E3"], p2, alpha, EV_F64_EVENTS, trajectory, calibration, stream,
+                          from_frames)
+    if refused == "repair":
+        out.update(bad_frame=w["bad_frame"], repaired=w["repaired"])
+    return out
 
 
 # ------------------------------------------------------------------ the batched filter
@@ -1557,13 +1716,22 @@ class PhoneSession(_ChunkedSession):
         return self._launch(ptrs[0], int(n2), ptrs[1], int(n3), trajectory, calibration, ptrs[2], int(n1),
                             records=records)
 
-    def feed_frames(self, frames_chunk, calibration=None, trajectory=False, records=False):
+    def feed_frames(self, frames_chunk, calibration=None, trajectory=False, records=False, refused="raise"):
         """The next [F][K][100] wire frames of the phones (wire.frames): parsed with a row per frame
         (wire_events(..., frame_rows=True): a frame's parse does not depend on earlier frames, and row f of each
         plane is frame f's message of that phase), then fed as feed_planes.  calibration: a dict, as feed;
         "frames" is refused -- without n_cal phase 1 is not chunked: calibrate first (calibrate_magnetometer), or
         construct the session with n_cal=, which then parses the chunk's phase-1 messages too
-        (wire_events(..., phase1=True)) and feeds ev1's first E1 rows.  records: as feed's."""
+        (wire_events(..., phase1=True)) and feeds ev1's first E1 rows.  records: as feed's.
+        refused: as wire_events.  "raise" (default): a frame the device parser does not take raises ValueError and
+        the chunk is fed to nobody.  "repair": the chunk is repaired as wire_events does it, and the returned tuple
+        gains two trailing items, bad_frame (K,) int32 -- -1, or the frame of THIS chunk that stopped the phone --
+        and repaired (K,) bool.  A phone that stops is marked in the session (session.stopped): its connection has
+        ended, as the server's process for it would have, so on every later feed_frames (in either mode) its
+        column is no-message rows in every plane, whatever the phone goes on sending, and its bad_frame is -1;
+        recycle(columns) clears the mark for the column's next phone, export_columns / import_columns / move and
+        snapshot / restore carry it.  feed and feed_planes take planes, not frames, and know nothing of it."""
+        _check_refused(refused)
         if isinstance(calibration, str) and self._phase1 is None:
             raise ValueError("a chunked session takes calibrate_magnetometer's dict: phase 1 from the frames "
                              "(calibration='frames') is not chunked in this session -- construct the session with "
@@ -1573,15 +1741,30 @@ class PhoneSession(_ChunkedSession):
         if Kf != self.batch:
             raise ValueError("the frames are of %d phones, the session of %d" % (Kf, self.batch))
         if F == 0:
-            return self._launch(None, 0, None, 0, trajectory, calibration, records=records)
+            out = self._launch(None, 0, None, 0, trajectory, calibration, records=records)
+            if refused == "repair":
+                out += (np.full(self.batch, -1, np.int32), np.zeros(self.batch, bool))
+            return out
+        stopped = self._book.get("stopped")
         if self._phase1 is not None:
-            w = wire_events(frames_chunk, None, True, phase1=True)
-            return self.feed_planes(w["ev2"], w["E2"], w["ev3"], w["E3"], trajectory, None,
-                                    offset3=32 * self.batch * w["ev3_from"], planes1=w["ev1"], n1=w["E1"],
-                                    records=records)
-        w = wire_events(frames_chunk, None, True)
-        return self.feed_planes(w["ev2"], w["E2"], w["ev3"], w["E3"], trajectory, calibration,
-                                offset3=32 * self.batch * w["ev3_from"], records=records)
+            w = wire_events(frames_chunk, None, True, phase1=True, refused=refused, stopped=stopped)
+            out = self.feed_planes(w["ev2"], w["E2"], w["ev3"], w["E3"], trajectory, None,
+                                   offset3=32 * self.batch * w["ev3_from"], planes1=w["ev1"], n1=w["E1"],
+                                   records=records)
+        else:
+            w = wire_events(frames_chunk, None, True, refused=refused, stopped=stopped)
+            out = self.feed_planes(w["ev2"], w["E2"], w["ev3"], w["E3"], trajectory, calibration,
+                                   offset3=32 * self.batch * w["ev3_from"], records=records)
+        if refused == "repair":
+            self._book["stopped"] = self.stopped | (w["bad_frame"] >= 0)
+            out += (w["bad_frame"], w["repaired"])
+        return out
+
+    @property
+    def stopped(self):
+        """(K,) bool, a copy: the phones whose stream a frame ended (feed_frames(refused="repair")) and whose column
+        has not been recycled since"""
+        return np.array(self._book.get("stopped", np.zeros(self.batch, bool)), bool)
 
     def _launch(self, ev2, E2, ev3, E3, trajectory, calibration, ev1=None, E1=0, records=False):
         K, f = self.batch, self.filters
@@ -1688,6 +1871,8 @@ class PhoneSession(_ChunkedSession):
         book["total_counts"][cols] = 0
         book["dt_sum"][cols] = 0.0
         book["t_init"][cols] = t0
+        if "stopped" in book:   # the next phone's connection is a new one
+            book["stopped"][cols] = False
         return out
 
     _BOOK_ROWS = ("t_init", "dt_sum", "total_counts")
@@ -1720,7 +1905,8 @@ class PhoneSession(_ChunkedSession):
             _launch_move(lib.pekf_session_export_dev, K, cols, EV_F64_EVENTS, pack, *self._move_groups())
         q, r = (np.full(n, f.q), np.full(n, f.r)) if f.noise is None else (f.q[cols].copy(), f.r[cols].copy())
         out = SessionColumns("phone", pack, n, self.n_avg, self.alpha, self.n_cal, "f64", q, r,
-                             {name: self._book[name][cols].copy() for name in self._BOOK_ROWS})
+                             dict({name: self._book[name][cols].copy() for name in self._BOOK_ROWS},
+                                  stopped=self.stopped[cols]))
         if release and n:
             self.recycle(cols)
         return out
@@ -1754,6 +1940,10 @@ class PhoneSession(_ChunkedSession):
         _launch_move(lib.pekf_session_import_dev, K, cols, EV_F64_EVENTS, pack.pack, *self._move_groups())
         for name in self._BOOK_ROWS:
             self._book[name][cols] = pack.book[name]
+        stopped = self.stopped   # (a pack from before the mark existed: none stopped)
+        stopped[cols] = pack.book.get("stopped", False)
+        if stopped.any() or "stopped" in self._book:
+            self._book["stopped"] = stopped
 
     def move(self, src, dst):
         """import_columns(dst, export_columns(src)) within this session: the phones of src go on in the columns

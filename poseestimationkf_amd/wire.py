@@ -163,5 +163,27 @@ def frames(texts, n_frames=None):
     return out
 
 
-__all__ = ["server_values", "parse", "java_float_string", "message", "events_text", "events_from_wire", "frames",
-           "FRAME"]
+# parse_frames' status per frame (include/pekf.h, PEKF_WIRE_*): what the server does with the frame
+NO_HASH, SHORT, THROWS, MESSAGE = 0, 1, 2, 3
+
+
+def parse_frames(frames):
+    """(n, 100) uint8 frames, each one message as the server's recv loop takes it (Server.cpp:84,97; a '\\n'
+    inside a frame does not split it, which parse's lines cannot express) -> dict(status (n,) uint8 -- NO_HASH: no
+    '#'; SHORT: 30 characters or fewer after it; THROWS: the server's std::stod / std::stoll would throw, which
+    ends that client's server process; MESSAGE: processed --, phase (n,) uint8, types (n,) uint8, values (n, 3)
+    float64, times (n,) int64: parse's fields for a processed frame, zeros for any other).  A frame that throws is
+    reported and the next one read (pekf_wire_parse_frames)."""
+    fr = np.ascontiguousarray(frames, np.uint8)
+    if fr.ndim != 2 or fr.shape[1] != FRAME:
+        raise ValueError("frames must be (n, %d) bytes" % FRAME)
+    n = fr.shape[0]
+    st, ph, ty = np.empty(n, np.uint8), np.empty(n, np.uint8), np.empty(n, np.uint8)
+    xyz, t = np.empty((n, 3), np.float64), np.empty(n, np.int64)
+    check(lib.pekf_wire_parse_frames(n, fr.ctypes.data, st.ctypes.data, ph.ctypes.data, ty.ctypes.data,
+                                     xyz.ctypes.data, t.ctypes.data))
+    return dict(status=st, phase=ph, types=ty, values=xyz, times=t)
+
+
+__all__ = ["server_values", "parse", "parse_frames", "java_float_string", "message", "events_text",
+           "events_from_wire", "frames", "FRAME", "NO_HASH", "SHORT", "THROWS", "MESSAGE"]
